@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — 512 px, 50-step character images / second on synthetic CMIGBench 4-turn stories (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]           # N = 1
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   # N = 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                    # one rank per GPU over RCCL
 
@@ -35,6 +35,7 @@ MFMA_PEAK_TFLOPS = 2500.0        # dense bf16/fp16, MI355X_MICROARCH.md
 SD15_FLOP_PER_CFG_CALL = 1.607e12  # 401.8 GMAC / sample, batch 2
 PLAN_FLOP_PER_CFG_CALL = {"sd15": 1.607e12, "sd21": 4.30e12, "sdxl": 13.56e12}      # SURVEY.md §8(d), batch-2 CFG unit
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md (6.3 TB/s achievable)
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: what a comparison of two builds reads back
 
 
 def parse():
@@ -46,7 +47,7 @@ def parse():
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--streams", type=int, default=1,
                     help="denoise the character batch as this many independent sub-batches replayed concurrently on separate "
-                         "HIP streams (same UNet weights).  2 is +2 % images/s, but every launch is then a half-batch call "
+                         "HIP streams (same UNet weights).  2 is +2 %% images/s, but every launch is then a half-batch call "
                          "overlapping with the other chain, so per-kernel roofline / rocprof figures are no longer those of "
                          "one kernel owning the chip: the default line keeps 1")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
@@ -75,7 +76,15 @@ def parse():
     ap.add_argument("--stage2", action="store_true",
                     help="NOT the north-star line: time the stage-2 step (ControlNet + IP-Adapter UNet, reference "
                          "pipelines.py:759-835) on the same stories instead of the stage-1 per-character step")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32): final_latents = "
+                         "the final latents [jobs, 4, 64, 64] of that step's (turn, character) jobs, 8 per story, one story per GPU under "
+                         "weak scaling (with --with-vae too: the decoded images are not written).  The inputs are seeded: two builds run with the "
+                         "same arguments can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def build_model(plan, dtype, device, num_tokens=4, scale=0.4):
@@ -706,6 +715,16 @@ def bench_sdxl(args):
     return result
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32, at most DUMP_MAX_BYTES in all"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    assert sum(a.nbytes for a in host.values()) <= DUMP_MAX_BYTES, {k: a.shape for k, a in host.items()}
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     args = parse()
     from theatergen_amd import distributed as D
@@ -714,6 +733,8 @@ def main():
     if args.plan in ("sd21", "sdxl"):
         if args.gpus != 1:
             raise SystemExit("bench.py: --plan sd21 / sdxl are single-GPU lines")
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs covers the story line (--plan sd15) only")
         torch.cuda.set_device(0)
         print(json.dumps(bench_sd21_editing(args) if args.plan == "sd21" else bench_sdxl(args)), flush=True)
         return
@@ -846,6 +867,8 @@ def main():
         sampler.__exit__()
     elapsed = D.max_over_ranks(elapsed, device)
     assert torch.isfinite(gathered).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"final_latents": gathered})
 
     images = jobs_per_story * args.steps * (1 if strong else world)
     value = images / elapsed

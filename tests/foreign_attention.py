@@ -99,3 +99,12 @@ class ForeignUNet(nn.Module):
 
         for name, module in self.named_children():
             rec(name, module, processor)
+
+
+class ReferenceShapedAttention(ForeignAttention):
+    """``ForeignAttention`` with the forward of the reference's OWN ``Attention`` (ip_adapter/attention_processor.py:156-167), which also hands its
+    processor ``return_attntion_probs`` (its spelling); the keywords it sends are checked against tests/golden/attention_attrs.npz"""
+
+    def forward(self, hidden_states, encoder_hidden_states=None, attention_mask=None, return_attntion_probs=False, **cross_attention_kwargs):
+        return self.processor(self, hidden_states, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask,
+                              return_attntion_probs=return_attntion_probs, **cross_attention_kwargs)

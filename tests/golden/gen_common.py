@@ -153,6 +153,28 @@ BRANCH_CASES = [
 ]
 
 
+# ---- host-independent comparisons ----
+# resampler_f64.npz: float64 reference outputs, stored as the fp32 golden + an int8 correction in steps of F64_STEP (rounding <= 6e-8)
+F64_STEP = 2.0 ** -23
+
+
+def fsum_checksum(tensors):
+    """exactly rounded sums, then sums of absolute values, of the tensors (math.fsum): the same bits on every host"""
+    return ([math.fsum(t.double().flatten().tolist()) for t in tensors] +
+            [math.fsum(t.double().abs().flatten().tolist()) for t in tensors])
+
+
+# ---- the processor boundary: constructor kwargs of the Attention modules whose attribute names attention_attrs.npz records (the last one
+# is the VAE mid-block usage, 4-D input) ----
+ATTR_CASES = [
+    dict(query_dim=64, heads=2, dim_head=32),
+    dict(query_dim=64, heads=2, dim_head=32, norm_num_groups=8, residual_connection=True, bias=True),
+    dict(query_dim=64, cross_attention_dim=32, heads=2, dim_head=32, cross_attention_norm="layer_norm"),
+    dict(query_dim=64, cross_attention_dim=32, heads=2, dim_head=32),
+    dict(query_dim=64, heads=2, dim_head=32, norm_num_groups=8, residual_connection=True, rescale_output_factor=2.0),
+]
+
+
 def branch_params(name, kw, cross, seed):
     """state dict (reference parameter names) + inputs of one branch case"""
     g = torch.Generator().manual_seed(seed)

@@ -525,85 +525,66 @@ def _fake_ops():
 
 
 class _AttrRecorder:
-    """forwards attribute reads to a REFERENCE Attention instance and records every name that instance does not have"""
+    """forwards attribute reads to a stand-in Attention instance and records every name the REFERENCE Attention does not have"""
 
-    def __init__(self, target):
+    def __init__(self, target, allowed):
         object.__setattr__(self, "_target", target)
+        object.__setattr__(self, "_allowed", allowed)
         object.__setattr__(self, "seen", set())
         object.__setattr__(self, "missing", set())
 
     def __getattr__(self, name):
         self.seen.add(name)
-        if not hasattr(self._target, name):
+        if name not in self._allowed:
             self.missing.add(name)
             raise AttributeError(name)
         return getattr(self._target, name)
 
 
-def _reference_attention_module():
-    """ip_adapter/attention_processor.py of the reference, imported by path with a stub `diffusers.utils` (build container only)"""
-    import importlib.util
-    import logging
-    import sys
-    import types
-    ref = os.environ.get("TG_REFERENCE", "/root/reference")
-    path = os.path.join(ref, "ip_adapter", "attention_processor.py")
-    if not os.path.exists(path):
-        import pytest
-        pytest.skip("the reference checkout is only present in the build container")
-    saved = {k: sys.modules.get(k) for k in ("diffusers", "diffusers.utils")}
-    du = types.ModuleType("diffusers.utils")
-    du.deprecate = lambda *a, **k: None
-    du.logging = types.SimpleNamespace(get_logger=logging.getLogger)
-    d = types.ModuleType("diffusers")
-    d.utils = du
-    d.__path__ = []
-    sys.modules.update({"diffusers": d, "diffusers.utils": du})
-    try:
-        spec = importlib.util.spec_from_file_location("ref_ip_attnproc_boundary", path)
-        m = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(m)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
-    return m
-
-
 def test_processors_touch_only_attributes_of_the_reference_attention(monkeypatch):
-    """SURVEY §8(b) / INTEGRATION.md level 2: our processors installed on the REFERENCE `Attention` (ip_adapter/attention_processor.py
-    :12-279).  Every attribute they read must exist on that class — `inner_dim` / `dim_head` / packed-weight helpers do not."""
+    """SURVEY §8(b) / INTEGRATION.md level 2: our processors installed on a diffusers-shaped `Attention` (tests/foreign_attention.py).  Every attribute
+    they read must exist on the REFERENCE class (ip_adapter/attention_processor.py:12-279; its names per constructor case, beyond those of a plain
+    `nn.Module`, are stored in tests/golden/attention_attrs.npz) — `inner_dim` / `dim_head` / packed-weight helpers do not."""
     import torch
+    from tests.foreign_attention import ForeignAttention, ReferenceShapedAttention
+    from tests.golden.gen_common import ATTR_CASES
     from theatergen_amd import attention_processor as AP
-    A = _reference_attention_module()
+    gold = _load("attention_attrs")
+    base = set(dir(torch.nn.Module()))
+
+    def recorder(ci):
+        return _AttrRecorder(ForeignAttention(**ATTR_CASES[ci]), base | set(gold[f"case{ci}"].tolist()))
     monkeypatch.setattr(AP, "ops", _fake_ops())
     monkeypatch.setattr(AP, "_need_gpu", lambda t: None)
     x = torch.zeros(2, 16, 64)
     enc = torch.zeros(2, 77 + 4, 32)
     cases = [
-        (A.Attention(query_dim=64, heads=2, dim_head=32), AP.AttnProcessor(), dict()),
-        (A.Attention(query_dim=64, heads=2, dim_head=32, norm_num_groups=8, residual_connection=True, bias=True), AP.AttnProcessor(),
-         dict(attention_mask=torch.zeros(2, 1, 16))),
-        (A.Attention(query_dim=64, cross_attention_dim=32, heads=2, dim_head=32, cross_attention_norm="layer_norm"), AP.AttnProcessor(),
+        (0, AP.AttnProcessor(), dict()),
+        (1, AP.AttnProcessor(), dict(attention_mask=torch.zeros(2, 1, 16))),
+        (2, AP.AttnProcessor(),
          dict(encoder_hidden_states=enc, save_attn_to_dict={}, attn_key=["mid", 0, 0, 0], return_cond_ca_only=True, return_token_ca_only=3)),
-        (A.Attention(query_dim=64, cross_attention_dim=32, heads=2, dim_head=32), AP.IPAttnProcessor(64, 32, scale=0.4, num_tokens=4),
-         dict(encoder_hidden_states=enc, save_attn_to_dict={}, attn_key=["mid", 0, 0, 0])),
-        (A.Attention(query_dim=64, cross_attention_dim=32, heads=2, dim_head=32), AP.CNAttnProcessor(num_tokens=4),
-         dict(encoder_hidden_states=enc)),
+        (3, AP.IPAttnProcessor(64, 32, scale=0.4, num_tokens=4), dict(encoder_hidden_states=enc, save_attn_to_dict={}, attn_key=["mid", 0, 0, 0])),
+        (3, AP.CNAttnProcessor(num_tokens=4), dict(encoder_hidden_states=enc)),
     ]
-    for ref_attn, proc, kw in cases:
-        rec = _AttrRecorder(ref_attn)
+    for ci, proc, kw in cases:
+        rec = recorder(ci)
         out = proc(rec, x, **kw)
         out = out[0] if isinstance(out, tuple) else out
         assert out.shape == x.shape
         assert not rec.missing, f"{type(proc).__name__} read attributes the reference Attention lacks: {sorted(rec.missing)}"
         assert {"heads", "to_q", "to_out"} <= rec.seen
-    # 4-D input (the VAE mid-block usage) on the reference module, dispatched through ITS set_processor / forward
-    ref_attn = A.Attention(query_dim=64, heads=2, dim_head=32, norm_num_groups=8, residual_connection=True, rescale_output_factor=2.0)
-    ref_attn.set_processor(AP.AttnProcessor())
-    assert ref_attn(torch.zeros(2, 64, 4, 4)).shape == (2, 64, 4, 4)
+    # 4-D input (the VAE mid-block usage): read only what the reference has, and dispatched through set_processor / forward with the keywords the
+    # reference forward passes (stored: forward.kwargs / forward.values; the reference-shaped stand-in must send exactly those)
+    rec = recorder(4)
+    assert AP.AttnProcessor()(rec, torch.zeros(2, 64, 4, 4)).shape == (2, 64, 4, 4)
+    assert not rec.missing, f"AttnProcessor (4-D) read attributes the reference Attention lacks: {sorted(rec.missing)}"
+    attn = ReferenceShapedAttention(**ATTR_CASES[4])
+    sent = {}
+    attn.set_processor(lambda a, h, **kw: sent.update(kw) or h)
+    attn(torch.zeros(2, 64, 4, 4))
+    assert sorted(sent) == gold["forward.kwargs"].tolist() and [repr(sent[k]) for k in sorted(sent)] == gold["forward.values"].tolist(), sent
+    attn.set_processor(AP.AttnProcessor())
+    assert attn(torch.zeros(2, 64, 4, 4)).shape == (2, 64, 4, 4)
 
 
 def test_ip_scale_is_a_plain_mutable_attribute():

@@ -108,10 +108,10 @@ def build(force=False, verbose=True, check_gate=False):
         _write_build_info()
     # The register / scratch gate: `python -m theatergen_amd.build --resources --check` (what the repository's own build entry, __graft_entry__.build(),
     # runs: check_gate=True) or TG_BUILD_GATE=1.  A plain build() — another compiler, a read-only or site-packages install — never fails on it and never
-    # has to write under profiles/ (ADVICE r4).
+    # has to write under profiles/ (ADVICE r4).  The gate checks the built objects without rewriting the committed report: a build leaves the tree
+    # as it found it (only `--resources` refreshes profiles/).
     if check_gate or os.environ.get("TG_BUILD_GATE") == "1":
-        if todo or not os.path.exists(RESOURCES_JSON):
-            write_resources(check=True, verbose=verbose)
+        write_resources(check=True, verbose=verbose, report=False)
     return LIB
 
 
@@ -307,19 +307,20 @@ def check_mfma_loops(verbose=True):
     return bad
 
 
-def write_resources(check=False, verbose=True):
+def write_resources(check=False, verbose=True, report=True):
     import json
     res = kernel_resources(verbose=verbose)
-    try:
-        commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], capture_output=True, text=True, cwd=HERE).stdout.strip()
-    except OSError:
-        commit = ""
-    try:
-        os.makedirs(os.path.dirname(RESOURCES_JSON), exist_ok=True)
-        with open(RESOURCES_JSON, "w") as f:
-            json.dump({"flags": FLAGS, "built_from_commit_or_later": commit, "gates": HOT_GATES, "kernels": dict(sorted(res.items()))}, f, indent=1)
-    except OSError as e:                                         # read-only tree: the report is optional, the check below is not
-        print(f"[resources] cannot write {RESOURCES_JSON}: {e}", flush=True)
+    if report:
+        try:
+            commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], capture_output=True, text=True, cwd=HERE).stdout.strip()
+        except OSError:
+            commit = ""
+        try:
+            os.makedirs(os.path.dirname(RESOURCES_JSON), exist_ok=True)
+            with open(RESOURCES_JSON, "w") as f:
+                json.dump({"flags": FLAGS, "built_from_commit_or_later": commit, "gates": HOT_GATES, "kernels": dict(sorted(res.items()))}, f, indent=1)
+        except OSError as e:                                     # read-only tree: the report is optional, the check below is not
+            print(f"[resources] cannot write {RESOURCES_JSON}: {e}", flush=True)
     bad = check_resources(res) + check_mfma_loops(verbose=verbose)
     for b in bad:
         print("[resources] GATE:", b, flush=True)

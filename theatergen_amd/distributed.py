@@ -126,7 +126,10 @@ def gather_latents(local, force=False):
 
 def barrier(force=False):
     if is_dist(force):
-        dist.barrier()
+        if dist.get_backend() == dist.Backend.GLOO:
+            dist.monitored_barrier()          # CPU group: dist.barrier() would start the GPU runtime in every rank only to pick a device
+        else:
+            dist.barrier()
 
 
 def max_over_ranks(value, device, force=False):

@@ -71,6 +71,9 @@ const char* tg_last_error(void);
  * Output: out[m * ldc + n] for n < n_split (n_split <= 0: all); columns n >= n_split are written
  *         TRANSPOSED per batch item, out_t[(b * (N - n_split) + n - n_split) * ldt + (m % rows_per_batch)]
  *         (the V^T operand of tg_attention).
+ * Alignment: a0, a1 and w must be 16-byte aligned (their rows are staged with 16-byte loads; TG_ERR_ARG otherwise).  out, out_t, bias,
+ *         bvec and res need 8 bytes; with 16 bytes and pitches (ldc, ldres, ldbvec) that are multiples of 8 elements the kernels take the
+ *         LDS-transposed epilogue and the ping-pong tiles, otherwise a direct epilogue on other tiles.
  * `workspace`: fp32 scratch of `workspace_bytes`, used when the kernel splits K (small-M layers);
  *         tg_gemm_workspace_bytes() gives the size needed for a descriptor.
  */

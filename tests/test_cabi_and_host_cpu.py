@@ -42,6 +42,21 @@ def test_argument_errors_map_to_runtime_error():
         _lib.check(rc)
     a = _lib.AttnDesc()
     assert h.tg_attention(C.byref(a), None) == -1
+    # A / W bases are staged with 16-byte loads: an 8-byte aligned a0, a1 or w is refused before any launch (fake pointers, never read)
+
+    def plain(a0=16, w=16, a1=None):
+        d = _lib.GemmDesc()
+        d.dtype, d.mode, d.a0, d.w, d.out, d.a1 = 0, 0, a0, w, 16, a1
+        d.M, d.N, d.K, d.c0, d.c1, d.ldc, d.out_scale = 256, 64, 128, 64 if a1 else 128, 64 if a1 else 0, 64, 1.0
+        return d
+    kk = C.c_int32()
+    assert h.tg_gemm_plan(C.byref(plain()), None, None, None, C.byref(kk)) == 0, h.tg_last_error()
+    assert h.tg_gemm_plan(C.byref(plain(a1=32)), None, None, None, C.byref(kk)) == 0, h.tg_last_error()
+    for bad in (plain(a0=24), plain(w=24), plain(a1=24), plain(a0=8, w=8)):
+        assert h.tg_gemm_plan(C.byref(bad), None, None, None, C.byref(kk)) == -1
+        assert b"16-byte aligned" in h.tg_last_error()
+        assert h.tg_gemm(C.byref(bad), None) == -1
+        assert h.tg_gemm_workspace_bytes(C.byref(bad)) == -1
 
 
 def test_no_cpu_fallback():

@@ -750,9 +750,16 @@ def test_conv_slab_kernel(dtype, case):
         else:
             os.environ["TG_SLAB_PP"] = old_pp
     check(out1.float().cpu().reshape(B, h, w, cout).permute(0, 3, 1, 2), ref, dtype, f"slab conv (one compute wave per SIMD) {case}")
-    pp_took_it = w in (16, 32, 64) and h % (128 // w) == 0  # default TG_SLAB_PP = 2: whole-row tiles of the 64 / 32 / 16-wide maps
-    if not pp_took_it:
-        assert torch.equal(out, out1), "patch tiles do not run on the ping-pong kernel"
+    # default TG_SLAB_PP = 3: whole-row tiles of the 64 / 32 / 16-wide maps AND the one-patch tiles of wider maps (64 / 32 / 16-pixel patches: the 80-,
+    # 96-, 128-wide cases) run on the two-wave kernel; only the two-patch tiles of 8-wide patches (8 x 8, 24 x 24) stay on conv_slab_kernel
+    whole_row = w in (16, 32, 64) and h % (128 // w) == 0
+    if not whole_row:
+        two_wave_patch = w % 16 == 0
+        assert torch.equal(out, out1), ("patch tiles: the two-wave kernel (TG_SLAB_PP=3) no longer reproduces conv_slab_kernel (TG_SLAB_PP=0) bit for bit"
+                                        if two_wave_patch else "two-patch tiles: conv_slab_kernel under both settings, outputs must be identical")
+        if two_wave_patch:
+            again = ops.conv3x3(x0, wp, B, h, w, cin, **fkw, **kw)
+            assert torch.equal(out, again), "the two-wave slab kernel is deterministic on patch tiles"
     else:
         check(out.float(), out1.float(), dtype, f"ping-pong slab vs one-wave slab {case}", scale=1.0)
         again = ops.conv3x3(x0, wp, B, h, w, cin, **fkw, **kw)

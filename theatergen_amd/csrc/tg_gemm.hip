@@ -560,6 +560,10 @@ int validate(const tg_gemm_desc* d) {
   TG_CHECK(d != nullptr, TG_ERR_ARG, "tg_gemm: null descriptor");
   TG_CHECK(d->dtype == TG_BF16 || d->dtype == TG_F16, TG_ERR_ARG, "tg_gemm: bad dtype %d", d->dtype);
   TG_CHECK(d->a0 && d->w && d->out, TG_ERR_ARG, "tg_gemm: null a0/w/out");
+  // A and W reach LDS through 16-byte requests (global_load_lds_dwordx4, dwordx4 window loads) at base + row * pitch + k with pitches and
+  // K-steps in multiples of 8 elements: the bases themselves must be 16-byte aligned
+  TG_CHECK((reinterpret_cast<uintptr_t>(d->a0) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->a1) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->w) & 15) == 0,
+           TG_ERR_ARG, "tg_gemm: a0 / a1 / w must be 16-byte aligned (a0=%p a1=%p w=%p)", d->a0, d->a1, d->w);
   TG_CHECK(d->M > 0 && d->N > 0 && d->K > 0, TG_ERR_ARG, "tg_gemm: empty problem M=%lld N=%lld K=%lld",
            (long long)d->M, (long long)d->N, (long long)d->K);
   TG_CHECK(d->N % 4 == 0 && d->K % 8 == 0, TG_ERR_ARG, "tg_gemm: N %% 4 and K %% 8 required (N=%lld K=%lld)",

@@ -43,7 +43,7 @@ extern "C" {
 
 /* ABI version: changes whenever a signature or descriptor layout in this header changes.  Callers compare it with the
  * TG_ABI_VERSION they were built against (the ctypes binding does at load time) and refuse a mismatching library. */
-#define TG_ABI_VERSION 307
+#define TG_ABI_VERSION 308
 int tg_version(void);
 const char* tg_last_error(void);
 
@@ -337,6 +337,36 @@ int tg_step_epilogue(const float* noise_pred, float* latents, int32_t n_img, int
                      int32_t has_cfg, float guidance_scale, const float* coef, int32_t* step_idx, int32_t advance,
                      int32_t prediction_type, const float* frozen, const float* frozen_mask, int32_t mask_per_img,
                      int32_t frozen_steps, float* history, void* model_in, int32_t model_in_dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Step epilogue of the sigma-parameterised schedulers (diffusers EulerDiscreteScheduler / EulerAncestralDiscreteScheduler,
+ * epsilon prediction): CFG combine, then
+ *   x' = x + eps * coef[s][0] + coef[s][1] * noise[s]        (Euler: coef[s][0] = sigma_{i+1} - sigma_i, coef[s][1] = 0;
+ *                                                              ancestral: sigma_down - sigma_i, sigma_up)
+ * with s = *step_idx (DEVICE int32, incremented when `advance`), then the frozen-mask blend while s < frozen_steps (as
+ * tg_step_epilogue), the history row s+1, and the next UNet input model_in = cat([x'] * 2) * coef[s][2] (the fp32 reciprocal
+ * 1 / sqrt(sigma_next^2 + 1) of scale_model_input's divisor) in model_in_dtype.  coef: DEVICE fp32 [n_steps][4] (coef[s][3] = sigma_i,
+ * informational).  noise (may be NULL): DEVICE [n_steps, n_img, C, h, w] in noise_dtype (TG_BF16, TG_F16 or 2 = fp32), the
+ * per-step ancestral draws the host made before the loop.  model_in_dtype: TG_BF16, TG_F16 or 2 = fp32.  Other arguments as
+ * tg_step_epilogue.
+ */
+int tg_step_epilogue_sigma(const float* noise_pred, float* latents, int32_t n_img, int32_t chw, int32_t hw,
+                           int32_t has_cfg, float guidance_scale, const float* coef, int32_t* step_idx, int32_t advance,
+                           const void* noise, int32_t noise_dtype, const float* frozen, const float* frozen_mask,
+                           int32_t mask_per_img, int32_t frozen_steps, float* history, void* model_in, int32_t model_in_dtype,
+                           void* stream);
+
+/* T2I-Adapter pieces (diffusers T2IAdapter "full_adapter_xl"), storage dtype in / out:
+ * tg_pixel_unshuffle: NCHW [batch, C, h, w] -> token-major [batch * (h/f) * (w/f), C f^2], channel c f^2 + i f + j from pixel
+ *                     (f y + i, f x + j) (F.pixel_unshuffle); pure data movement.
+ * tg_relu           : out = max(x, 0) over n elements (may alias).
+ * tg_avgpool2x2     : AvgPool2d(2, 2, ceil_mode=True) on token-major [batch * h * w, C] -> [batch * ceil(h/2) * ceil(w/2), C].
+ * tg_scale_repeat   : out[r * n + i] = x[i] * scale for r < copies (conditioning scale + CFG duplication). */
+int tg_pixel_unshuffle(int32_t dtype, const void* in, int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t factor,
+                       void* out, void* stream);
+int tg_relu(int32_t dtype, const void* x, int64_t n, void* out, void* stream);
+int tg_avgpool2x2(int32_t dtype, const void* x, int32_t batch, int32_t h, int32_t w, int32_t channels, void* out, void* stream);
+int tg_scale_repeat(int32_t dtype, const void* x, int64_t n, float scale, int32_t copies, void* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Input-gradient kernels of `latent_backward_guidance` (models/pipelines.py:62-128: autograd.grad(loss, [latents]) through the

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("THEATERGEN_HIP_LIB") or os.path.join(HERE, "lib", "libtheatergen_hip.so")
 
 TG_BF16, TG_F16 = 0, 1
-ABI_VERSION = 307          # TG_ABI_VERSION of include/theatergen_hip.h this binding was written against
+ABI_VERSION = 308          # TG_ABI_VERSION of include/theatergen_hip.h this binding was written against
 ACT_NONE, ACT_SILU, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2, 3
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -158,6 +158,11 @@ SIGNATURES = {
     "tg_conv_out_takes_coef": (i32, [i32, i32, i32, i32]),
     "tg_timestep_embedding": (i32, [i32, vp, vp, i32, i32, i32, i32, f32, vp, i64, vp]),
     "tg_step_epilogue": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, vp]),
+    "tg_step_epilogue_sigma": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp]),
+    "tg_pixel_unshuffle": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "tg_relu": (i32, [i32, vp, i64, vp, vp]),
+    "tg_avgpool2x2": (i32, [i32, vp, i32, i32, i32, i32, vp, vp]),
+    "tg_scale_repeat": (i32, [i32, vp, i64, f32, i32, vp, vp]),
     "tg_blend_latents": (i32, [vp, vp, vp, i32, i32, f32, f32, i32, vp, vp]),
     "tg_shift": (i32, [vp, i64, i32, i32, i32, i32, vp, vp]),
     "tg_masked_compose": (i32, [vp, vp, vp, i64, i32, vp]),

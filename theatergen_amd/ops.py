@@ -704,6 +704,55 @@ def step_epilogue(noise_pred, latents, guidance_scale, coef, step_idx, *, has_cf
                                            mask_per_img, int(frozen_steps), _ptr(history), _ptr(model_in), mi_dt, _stream()))
 
 
+def step_epilogue_sigma(noise_pred, latents, guidance_scale, coef, step_idx, *, has_cfg=True, advance=True, noise=None, frozen=None,
+                        frozen_mask=None, frozen_steps=0, history=None, model_in=None):
+    """Euler / Euler-ancestral step (``tg_step_epilogue_sigma``): ``coef`` = the scheduler's ``coef_table`` on the device, ``noise`` =
+    the pre-drawn ancestral noise table [n_steps, n_img, C, h, w] (storage dtype or fp32) or None"""
+    n_img = latents.shape[0]
+    chw = latents[0].numel()
+    hw = latents.shape[-1] * latents.shape[-2]
+    mask_per_img = 1 if (frozen_mask is not None and frozen_mask.numel() == n_img * hw and n_img > 1) else 0
+    mi_dt = -1 if model_in is None else _SRC[model_in.dtype]
+    nz_dt = -1 if noise is None else _SRC[noise.dtype]
+    _lib.check(_lib.lib().tg_step_epilogue_sigma(_ptr(noise_pred), _ptr(latents), n_img, chw, hw, 1 if has_cfg else 0, float(guidance_scale),
+                                                 _ptr(coef), _ptr(step_idx), 1 if advance else 0, _ptr(noise), nz_dt, _ptr(frozen),
+                                                 _ptr(frozen_mask), mask_per_img, int(frozen_steps), _ptr(history), _ptr(model_in), mi_dt,
+                                                 _stream()))
+
+
+def pixel_unshuffle(x, factor):
+    """NCHW [B, C, h, w] (bf16 / fp16) -> token-major [B * (h/f) * (w/f), C f^2] (``F.pixel_unshuffle`` then NHWC)"""
+    _need_cuda(x)
+    B, ch, h, w = x.shape
+    x = x.contiguous()
+    out = torch.empty((B * (h // factor) * (w // factor), ch * factor * factor), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.lib().tg_pixel_unshuffle(_dt(x), _ptr(x), B, ch, h, w, int(factor), _ptr(out), _stream()))
+    return out
+
+
+def relu(x, out=None):
+    if out is None:
+        out = torch.empty_like(x)
+    _lib.check(_lib.lib().tg_relu(_dt(x), _ptr(x), x.numel(), _ptr(out), _stream()))
+    return out
+
+
+def avgpool2x2(x, batch, h, w):
+    """AvgPool2d(2, 2, ceil_mode=True) of token-major [batch * h * w, C] -> [batch * ceil(h/2) * ceil(w/2), C]"""
+    ch = x.shape[-1]
+    out = torch.empty((batch * ((h + 1) // 2) * ((w + 1) // 2), ch), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.lib().tg_avgpool2x2(_dt(x), _ptr(x), batch, h, w, ch, _ptr(out), _stream()))
+    return out
+
+
+def scale_repeat(x, scale, copies, out=None):
+    """``cat([x * scale] * copies)`` along the leading dimension (x contiguous)"""
+    if out is None:
+        out = torch.empty((copies * x.shape[0], *x.shape[1:]), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.lib().tg_scale_repeat(_dt(x), _ptr(x), x.numel(), float(scale), int(copies), _ptr(out), _stream()))
+    return out
+
+
 def blend_latents(bg, fg, mask, ratio, sigma=1.0, storage_dtype=None):
     """fp32 in / out; ``storage_dtype`` torch.float16 / torch.bfloat16: reproduce the half-precision roundings of the
     reference expression (its latents are ``unet.dtype`` tensors)"""

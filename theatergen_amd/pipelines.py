@@ -17,7 +17,7 @@ import torch
 
 from . import ops
 from .attention_processor import register_replay_stream, tensor_version, unregister_replay_stream
-from .scheduler import DDIMScheduler
+from .scheduler import DDIMScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler
 from .unet import DeviceSchedule
 
 
@@ -76,7 +76,11 @@ class DenoiseEngine:
         self.dev, self.dt = dev, dt
         C = cfg.in_channels
         self.scheduler.set_timesteps(num_inference_steps)
-        self.timesteps = self.scheduler.timesteps.clone() if timesteps is None else torch.as_tensor(timesteps, dtype=torch.int64).clone()
+        # DDIM: the reference's own update; Euler / Euler ancestral (the SDXL flow): sigma-parameterised update, tg_step_epilogue_sigma
+        self.kind = ("euler_a" if isinstance(self.scheduler, EulerAncestralDiscreteScheduler) else
+                     "euler" if isinstance(self.scheduler, EulerDiscreteScheduler) else "ddim")
+        tdt = torch.int64 if self.kind == "ddim" else torch.float32
+        self.timesteps = self.scheduler.timesteps.clone() if timesteps is None else torch.as_tensor(timesteps, dtype=tdt).clone()
         num_inference_steps = self.steps = int(self.timesteps.numel())
         self.t_table = self.timesteps.to(device=dev, dtype=torch.float32)
         self.coef = self.scheduler.coef_table(self.timesteps).to(dev)
@@ -100,6 +104,14 @@ class DenoiseEngine:
         self.pred_type = 0 if self.scheduler.config.prediction_type == "epsilon" else 1
         self._tproj_table = None
         self._tproj_key = None
+        self.adapter_feats = None      # T2I-Adapter features: static CFG-duplicated token-major buffers (set_adapter)
+        self.step_noise = None         # Euler ancestral: the per-step noise table (set_step_noise)
+        self._noise_set = False
+        if self.kind != "ddim":
+            # scale_model_input of step 0 (the epilogue writes the later ones): x / sqrt(sigma_0^2 + 1)
+            self.in_div0 = float(self.scheduler.model_input_divisor(self.scheduler.index_for_timestep(self.timesteps[0], self.timesteps)))
+        if self.kind == "euler_a":
+            self.step_noise = torch.zeros((num_inference_steps, n_img, C, self.h, self.w), dtype=dt, device=dev)
 
     # ---- conditioning -----------------------------------------------------------------------------------
     def set_conditioning(self, encoder_hidden_states, added_cond_kwargs=None):
@@ -128,6 +140,39 @@ class DenoiseEngine:
             self.graph = None          # the scale is a launch constant of the zero-conv epilogues
         self.cn_scale = float(conditioning_scale)
         self.controlnet.cond_embedding(self.cn_cond, static=True)
+
+    def set_adapter(self, features, conditioning_scale=1.0):
+        """T2I-Adapter features of the ``n_img`` images (``T2IAdapter(..., token_major=True)`` ``_Act``s with batch n_img, or NCHW tensors):
+        ``state * conditioning_scale`` then ``cat([state] * 2)`` (CFG; reference models/pipelines.py:673-677) into static token-major buffers the
+        captured step adds into the UNet (``down_block_additional_residuals`` every step, no mid residual).  ``None`` removes them."""
+        from .unet import _Act
+        if features is None:
+            if self.adapter_feats is not None:
+                self.adapter_feats, self.graph = None, None
+            return
+        acts = []
+        for f in features:
+            if not isinstance(f, _Act):
+                b, c, h, w = f.shape
+                t = ops.transpose(f.to(self.dt).contiguous(), b, c, h * w).reshape(b * h * w, c)
+                f = _Act(t, b, h, w, c)
+            if f.b != self.n_img or f.t.dtype != self.dt:
+                raise ValueError(f"set_adapter: features must have batch {self.n_img} and dtype {self.dt}")
+            acts.append(f)
+        geo = [(f.h, f.w, f.c) for f in acts]
+        if self.adapter_feats is None or [(f.h, f.w, f.c) for f in self.adapter_feats] != geo:
+            self.adapter_feats = [_Act(torch.empty((2 * f.b * f.hw, f.c), dtype=self.dt, device=self.dev), 2 * f.b, f.h, f.w, f.c) for f in acts]
+            self.graph = None                                       # a captured step holds the old buffers' addresses
+        for dst, f in zip(self.adapter_feats, acts):
+            ops.scale_repeat(f.t.contiguous(), conditioning_scale, 2, out=dst.t)
+
+    def set_step_noise(self, table):
+        """Euler ancestral: the noise of every step, [steps, n_img, C, h, w] (``randn(model_output.shape, dtype=model_output.dtype, generator=g)``
+        drawn per step by the caller in the reference's generator order), copied into the static table the captured step reads"""
+        if self.kind != "euler_a":
+            raise RuntimeError("set_step_noise: only an Euler-ancestral engine draws noise in its step")
+        self.step_noise.copy_(table.reshape(self.step_noise.shape))
+        self._noise_set = True
 
     def _refresh_kv(self):
         self.unet.register_conditioning(self.enc)              # cache keyed by the tensor OBJECT self.enc (never its address)
@@ -191,9 +236,16 @@ class DenoiseEngine:
         tp = None
         if self._tproj_table is not None:
             tp = torch.index_select(self._tproj_table, 0, self.step_idx)[0]        # this step's row, by the DEVICE step counter (graph-replayable)
+        if self.adapter_feats is not None:
+            down = self.adapter_feats                                          # T2I-Adapter mode: mid stays None
         noise_pred = self.unet(self.model_in, self.sched, self.enc, added_cond_kwargs=self.added, return_dict=False,
                                out_dtype=torch.float32, down_block_additional_residuals=down,
                                mid_block_additional_residual=mid, time_proj=tp)[0]
+        if self.kind != "ddim":
+            ops.step_epilogue_sigma(noise_pred, self.latents, self.g, self.coef, self.step_idx, advance=True, noise=self.step_noise,
+                                    frozen=self.frozen, frozen_mask=self.frozen_mask, frozen_steps=self.frozen_steps, history=self.history,
+                                    model_in=self.model_in)
+            return
         ops.step_epilogue(noise_pred, self.latents, self.g, self.coef, self.step_idx, advance=True,
                           prediction_type=self.pred_type, frozen=self.frozen,
                           frozen_mask=self.frozen_mask, frozen_steps=self.frozen_steps, history=self.history,
@@ -209,6 +261,12 @@ class DenoiseEngine:
     def _reset(self, latents):
         self.latents.copy_(latents.to(device=self.dev, dtype=torch.float32))
         self.history[0].copy_(self.latents)
+        if self.kind != "ddim":
+            x0 = self.latents / self.in_div0                      # scale_model_input of step 0, then the `.half()`
+            self.model_in[:self.n_img].copy_(x0)
+            self.model_in[self.n_img:].copy_(x0)
+            self.step_idx.zero_()
+            return
         self.model_in[:self.n_img].copy_(self.latents)           # dtype cast on copy = the `.half()` of pipelines.py:414
         self.model_in[self.n_img:].copy_(self.latents)
         self.step_idx.zero_()
@@ -276,6 +334,8 @@ class DenoiseEngine:
         ``before_step(i)`` (optional) runs on the host before step i is launched — the place of the per-step
         ``set_scale(0.0)`` / ``set_scale(s)`` gating of reference ``ip_adapter/custom_pipelines.py:328-333``; the IP scale is a
         device scalar, so the same captured graph replays whatever it is set to."""
+        if self.kind == "euler_a" and not self._noise_set:
+            raise RuntimeError("DenoiseEngine (Euler ancestral): set_step_noise(...) before run(): the step noise is drawn on the host in the reference's order")
         with torch.no_grad():
             self._ensure_graph(latents)
             self._reset(latents)
@@ -323,14 +383,18 @@ def _own_unet(adapter, what):
     return unet
 
 
-def _engine_of(adapter, **kw):
-    """one engine (static buffers + captured step graph) per loop geometry, kept on the adapter: the characters of a run replay the same graph"""
+def _engine_of(adapter, unet=None, scheduler=None, **kw):
+    """one engine (static buffers + captured step graph) per loop geometry, kept on the adapter: the characters of a run replay the same graph.
+    Keyed on the UNet and the scheduler (identity and kind) too: stage 2 of the SDXL flow runs ``controlnetpipe.unet`` with the Euler-ancestral
+    scheduler of ``controlnetpipe``, stage 1 ``adapter.pipe.unet`` with its Euler scheduler (default: ``adapter.pipe``'s)."""
+    unet = adapter.pipe.unet if unet is None else unet
+    scheduler = adapter.pipe.scheduler if scheduler is None else scheduler
     cache = adapter.__dict__.setdefault("_tg_engines", {})
-    ts = kw.get("timesteps")
     key = tuple(sorted((k, (tuple(v.tolist()) if k == "timesteps" and v is not None else (id(v) if k == "controlnet" else v))) for k, v in kw.items()))
+    key += (("unet", id(unet)), ("scheduler", id(scheduler), type(scheduler).__name__))
     eng = cache.get(key)
-    if eng is None or eng.unet is not adapter.pipe.unet:
-        eng = cache[key] = DenoiseEngine(adapter.pipe.unet, adapter.pipe.scheduler, **kw)
+    if eng is None or eng.unet is not unet or eng.scheduler is not scheduler:
+        eng = cache[key] = DenoiseEngine(unet, scheduler, **kw)
     return eng
 
 
@@ -364,13 +428,12 @@ def generate_semantic_guidance(task, fg_seed_now, basever, ip_prompt, database_p
     ``adapter.get_image_embeds`` and ``adapter.pipe.encode_prompt``.  Device: the whole loop :406-453 is ``num_inference_steps`` replays of ONE captured
     step (UNet CFG call + fused CFG / DDIM epilogue + history row) — no ``.cpu()`` per step; the 51 latents come back in one copy when
     ``offload_latents_to_cpu`` asks for them on the host.  ``cross_attention_kwargs`` is ``None`` in the reference's UNet call (:428), so no map is
-    ever saved: ``saved_attns`` is the reference's list of empty dicts.  Unsupported here, loudly: the ``'xl'`` branch (multi-device ``.to('cuda:1')``
-    placement; the SDXL loop lives in ``theatergen_amd.custom_pipelines``) and ``return_cross_attn`` (an attribute no diffusers output has)."""
+    ever saved: ``saved_attns`` is the reference's list of empty dicts.  ``basever='xl'``: the SDXL branch (``_semantic_guidance_xl``).  Unsupported
+    here, loudly: ``return_cross_attn`` (an attribute no diffusers output has)."""
     from PIL import Image
     from . import schedule as tg_schedule
     if basever == "xl":
-        raise NotImplementedError("theatergen_amd.pipelines.generate_semantic_guidance: the 'xl' branch (models/pipelines.py:261-366, 466-470) is not on "
-                                  "this path; SDXL runs through theatergen_amd.custom_pipelines.StableDiffusionXLCustomPipeline")
+        _check_xl_stage1(adapter)
     if return_cross_attn:
         raise NotImplementedError("return_cross_attn reads unet_output.cross_attention_probs_* (models/pipelines.py:431-434), which the UNet call of "
                                   "the reference never fills; the saved-map side channel is save_attn_to_dict")
@@ -386,6 +449,9 @@ def generate_semantic_guidance(task, fg_seed_now, basever, ip_prompt, database_p
         scale, have_reffer = 0, 0
     adapter.set_scale(scale)
     prompt = ("single object, " if task == "editing" else "full-body picture of ") + str(ip_prompt)
+    if basever == "xl":
+        return _semantic_guidance_xl(adapter, unet, prompt, image, have_reffer, database_path, obj_id, fg_seed_now, num_inference_steps, guidance_scale,
+                                     fast_after_steps, fast_rate, return_saved_cross_attn, return_box_vis, save_all_latents, offload_latents_to_cpu)
     enc = _text_and_image_rows(adapter, prompt, SINGLE_OBJECT_NEGATIVE_PROMPT, image)
     # ---- the loop
     scheduler = adapter.pipe.scheduler
@@ -414,6 +480,151 @@ def generate_semantic_guidance(task, fg_seed_now, basever, ip_prompt, database_p
         allv = hist.to(latents.dtype).clone()
         ret.append(allv.cpu() if offload_latents_to_cpu else allv)
     return tuple(ret)
+
+
+def _check_xl_stage1(adapter):
+    """up front, before any encoding: the SDXL branch of stage 1 needs this package's SDXL UNet (``text_time`` plan) and Euler scheduler"""
+    from .unet import UNet2DConditionModel
+    unet = getattr(adapter.pipe, "unet", None)
+    if not isinstance(unet, UNet2DConditionModel) or unet.config.addition_embed_type != "text_time":
+        raise NotImplementedError("theatergen_amd.pipelines.generate_semantic_guidance('xl'): adapter.pipe.unet must be a theatergen_amd UNet2DConditionModel "
+                                  "with an SDXL (addition_embed_type='text_time') plan, e.g. from_state_dict(config.sdxl(), ...)")
+    if not isinstance(adapter.pipe.scheduler, EulerDiscreteScheduler) or isinstance(adapter.pipe.scheduler, EulerAncestralDiscreteScheduler):
+        raise NotImplementedError("theatergen_amd.pipelines.generate_semantic_guidance('xl'): adapter.pipe.scheduler must be a "
+                                  f"theatergen_amd.scheduler.EulerDiscreteScheduler (the SDXL base scheduler), got {type(adapter.pipe.scheduler).__name__}")
+
+
+def _xl_added_cond(pooled, negative_pooled, height, width, dev, dtype):
+    """``added_cond_kwargs`` of the SDXL loops (models/pipelines.py:321-345, 677-691): pooled rows [negative ; positive], time ids (H, W, 0, 0, H, W) twice"""
+    text_embeds = torch.cat([negative_pooled, pooled], dim=0).to(dev, dtype)
+    ids = torch.tensor([[float(height), float(width), 0.0, 0.0, float(height), float(width)]], dtype=torch.float32)
+    return {"text_embeds": text_embeds, "time_ids": torch.cat([ids, ids], dim=0).repeat(pooled.shape[0], 1).to(dev)}
+
+
+def _decode_pil(pipe, vae, latents):
+    """``vae.decode(latents / scaling_factor)`` in the VAE's own dtype -> ``pipe.image_processor.postprocess(image, output_type='pil')`` (a list)"""
+    vdt = getattr(vae, "dtype", latents.dtype)
+    decoded = vae.decode(latents.to(vdt) / vae.config.scaling_factor, return_dict=False)[0].detach()
+    post = getattr(getattr(pipe, "image_processor", None), "postprocess", None)
+    return post(decoded, output_type="pil") if post is not None else [_to_pil(decoded[i:i + 1]) for i in range(decoded.shape[0])]
+
+
+def _semantic_guidance_xl(adapter, unet, prompt, image, have_reffer, database_path, obj_id, fg_seed_now, num_inference_steps, guidance_scale,
+                          fast_after_steps, fast_rate, return_saved_cross_attn, return_box_vis, save_all_latents, offload_latents_to_cpu):
+    """Stage 1, SDXL (models/pipelines.py:204-214, 255-366, 372-453, 459-477).  The caller's ``latents`` are not used: the start latents are
+    ``randn([1, 4, H/8, W/8], generator=Generator(device).manual_seed(fg_seed_now), dtype=embeds dtype) * init_noise_sigma`` with H = W =
+    ``sample_size * vae_scale_factor``; Euler steps; a fast schedule replaces ``timesteps`` and keeps the full ``sigmas`` (step i uses sigmas[i])."""
+    from . import schedule as tg_schedule
+    pipe = adapter.pipe
+    scheduler = pipe.scheduler
+    dev, dtype = unet.device, unet.dtype
+    img, unc = adapter.get_image_embeds(pil_image=image, clip_image_embeds=None)
+    pos, neg, pooled, neg_pooled = pipe.encode_prompt(prompt, num_images_per_prompt=1, do_classifier_free_guidance=True,
+                                                      negative_prompt=SINGLE_OBJECT_NEGATIVE_PROMPT)
+    enc = prepare_ip_embeds(pos, neg, img.to(pos.device), unc.to(pos.device))
+    height = width = unet.config.sample_size * pipe.vae_scale_factor
+    scheduler.set_timesteps(num_inference_steps)
+    generator = torch.Generator(dev).manual_seed(fg_seed_now)
+    lat0 = torch.randn((1, unet.config.in_channels, height // 8, width // 8), generator=generator, device=dev, dtype=enc.dtype)
+    lat0 = lat0 * scheduler.init_noise_sigma.to(dev)                                                      # prepare_latents (:307-316)
+    timesteps = None
+    if fast_after_steps is not None:
+        timesteps = tg_schedule.get_fast_schedule(scheduler.timesteps, fast_after_steps, fast_rate)
+    eng = _engine_of(adapter, unet=unet, scheduler=scheduler, n_img=1, height=height, width=width, num_inference_steps=num_inference_steps,
+                     guidance_scale=guidance_scale, enc_len=enc.shape[1], timesteps=timesteps)
+    eng.set_conditioning(enc.to(dev, dtype), _xl_added_cond(pooled, neg_pooled, height, width, dev, dtype))
+    hist = eng.run(lat0)
+    out = hist[-1].to(dtype)                                                                              # `latents.half()` (:457)
+    images = _decode_pil(pipe, pipe.vae, out)[0]
+    if have_reffer == 0:
+        images.save(database_path + str(obj_id) + ".png")
+    ret = [out, images]
+    if return_saved_cross_attn:
+        ret.append([{} for _ in range(eng.steps)])
+    if return_box_vis:
+        ret.append(images)
+    if save_all_latents:
+        allv = hist.to(lat0.dtype).clone()
+        ret.append(allv.cpu() if offload_latents_to_cpu else allv)
+    return tuple(ret)
+
+
+def _adapter_image(image, height, width):
+    """diffusers ``_preprocess_adapter_image``: PIL -> Lanczos resize to (width, height) -> [0, 1] fp32 NCHW (an ndarray or a tensor as given)"""
+    import numpy as np
+    from PIL import Image
+    if torch.is_tensor(image):
+        return image
+    if not isinstance(image, Image.Image):
+        image = Image.fromarray(np.asarray(image))
+    arr = np.array(image.resize((width, height), resample=Image.LANCZOS))
+    arr = arr[None, ..., None] if arr.ndim == 2 else arr[None]
+    return torch.from_numpy(arr.astype(np.float32) / 255.0).permute(0, 3, 1, 2).contiguous()
+
+
+def _check_xl_stage2(adapter, controlnetpipe):
+    """up front, before any encoding: what the SDXL branch of stage 2 runs on must be this package's"""
+    from .t2i_adapter import T2IAdapter
+    from .unet import UNet2DConditionModel
+    unet = getattr(controlnetpipe, "unet", None)
+    if not isinstance(unet, UNet2DConditionModel) or unet.config.addition_embed_type != "text_time":
+        raise NotImplementedError("theatergen_amd.pipelines.final_image_generation('xl'): controlnetpipe.unet must be a theatergen_amd UNet2DConditionModel "
+                                  "with an SDXL (addition_embed_type='text_time') plan")
+    if not isinstance(getattr(controlnetpipe, "adapter", None), T2IAdapter):
+        raise NotImplementedError("theatergen_amd.pipelines.final_image_generation('xl'): controlnetpipe.adapter must be a theatergen_amd.t2i_adapter.T2IAdapter, "
+                                  f"got {type(getattr(controlnetpipe, 'adapter', None)).__name__}")
+    if not isinstance(getattr(controlnetpipe, "scheduler", None), EulerAncestralDiscreteScheduler):
+        raise NotImplementedError("theatergen_amd.pipelines.final_image_generation('xl'): controlnetpipe.scheduler must be a "
+                                  "theatergen_amd.scheduler.EulerAncestralDiscreteScheduler")
+    if not isinstance(adapter.pipe.scheduler, EulerDiscreteScheduler) or isinstance(adapter.pipe.scheduler, EulerAncestralDiscreteScheduler):
+        raise NotImplementedError("theatergen_amd.pipelines.final_image_generation('xl'): adapter.pipe.scheduler must be a "
+                                  "theatergen_amd.scheduler.EulerDiscreteScheduler (its timesteps, add_noise and init_noise_sigma are used)")
+
+
+def _final_image_xl(processor, controlnetpipe, overall_prompt, overall_negative_prompt, height, width, bg_seed, inp_mask, input_img, adapter, latents_all,
+                    num_inference_steps, frozen_steps, guidance_scale):
+    """Stage 2, SDXL (models/pipelines.py:592-700, 733-857): T2I-Adapter-XL + ``controlnetpipe.unet`` + Euler-ancestral steps, text rows only."""
+    import numpy as np
+    unet, t2i, euler_a, euler = controlnetpipe.unet, controlnetpipe.adapter, controlnetpipe.scheduler, adapter.pipe.scheduler
+    dev, dtype = unet.device, unet.dtype
+    generator = torch.Generator(dev).manual_seed(bg_seed)
+    euler.set_timesteps(num_inference_steps)
+    euler_a.set_timesteps(num_inference_steps)
+    if not torch.equal(euler.timesteps, euler_a.timesteps):
+        raise ValueError("final_image_generation('xl'): adapter.pipe.scheduler and controlnetpipe.scheduler must have the same timesteps")
+    h8, w8 = int(height / 8), int(width / 8)
+    m = np.array(inp_mask.resize((h8, w8)).convert("L")).astype(np.float32) / 255.0
+    m[m > 0] = 1
+    my_mask = torch.from_numpy(1 - m).to(device=dev, dtype=torch.float32)
+    img = torch.from_numpy(np.array(input_img).astype(np.float32) / 255.0)[None].permute(0, 3, 1, 2)
+    myimage = (2.0 * img - 1.0).to(device=dev, dtype=dtype)
+    vae = controlnetpipe.vae
+    # generator A (bg_seed): posterior sample, re-noising noise, the background draw the SDXL branch never uses (:617-632)
+    init_latents = vae.config.scaling_factor * vae.encode(myimage).latent_dist.sample(generator=generator)
+    noise = torch.randn(init_latents.shape, generator=generator, device=dev, dtype=dtype)
+    my_latents = euler.add_noise(init_latents, noise, euler.timesteps).unsqueeze(1)                      # [steps, 1, C, h, w]
+    torch.randn((1, unet.config.in_channels, h8, w8), generator=generator, device=dev, dtype=dtype)
+    control_image = processor(np.array(input_img), detect_resolution=384, image_resolution=1024)
+    adapter_input = _adapter_image(control_image, height, width).to(device=dev, dtype=dtype)
+    pos, neg, pooled, neg_pooled = controlnetpipe.encode_prompt(prompt=overall_prompt, num_images_per_prompt=1, do_classifier_free_guidance=True,
+                                                                negative_prompt=overall_negative_prompt)
+    # generator B (bg_seed again): the start latents, then one ancestral draw per step (:654-667, extra_step_kwargs)
+    generator = torch.Generator(dev).manual_seed(bg_seed)
+    start = torch.randn((1, unet.config.in_channels, h8, w8), generator=generator, device=dev, dtype=pos.dtype) * euler_a.init_noise_sigma.to(dev)
+    step_noise = torch.stack([torch.randn((1, unet.config.in_channels, h8, w8), generator=generator, device=dev, dtype=dtype)
+                              for _ in range(len(euler.timesteps))])
+    feats = t2i(adapter_input, token_major=True)
+    latents_all[0] = start.to(latents_all.device, latents_all.dtype)
+    latents_all[1:] = my_latents.to(latents_all.device, latents_all.dtype)
+    enc = torch.cat([neg, pos], dim=0).to(dev, dtype)
+    eng = _engine_of(adapter, unet=unet, scheduler=euler_a, n_img=1, height=height, width=width, num_inference_steps=num_inference_steps,
+                     guidance_scale=guidance_scale, enc_len=enc.shape[1], timesteps=euler.timesteps)
+    eng.set_conditioning(enc, _xl_added_cond(pooled, neg_pooled, height, width, dev, dtype))
+    eng.set_adapter(feats, 0.8)                                                                           # adapter_conditioning_scale (:674-675)
+    eng.set_step_noise(step_noise)
+    eng.set_frozen(latents_all.to(dev, torch.float32), my_mask, frozen_steps)
+    latents = eng.run(start)[-1].to(dtype)
+    return latents, _decode_pil(controlnetpipe, vae, latents)
 
 
 def _control_image(controlnetpipe, control_image, width, height, device, dtype):
@@ -445,11 +656,13 @@ def final_image_generation(basever, processor, controlnetpipe, tpipe, overall_pr
     (:605-614), not the ``frozen_mask`` argument; the start latents are fresh background noise (:632); IP scale 0.1 on the first character's image
     (:700-701); ControlNet at scale 1 on ``processor(input_img)`` every step (:705-731, 762-778).  All random draws come from the DEVICE generator
     seeded with ``bg_seed`` (:594, 625-632), in the reference's order.  Device: one captured step (ControlNet + UNet + CFG / DDIM / frozen-mask
-    replace) replayed ``num_inference_steps`` times; no per-step ``.cpu()`` (:835)."""
+    replace) replayed ``num_inference_steps`` times; no per-step ``.cpu()`` (:835).  ``basever='xl'``: the SDXL branch (``_final_image_xl``),
+    returns ``(latents, list of PIL images)`` as the reference does."""
     import numpy as np
     if basever == "xl":
-        raise NotImplementedError("theatergen_amd.pipelines.final_image_generation: the 'xl' branch (T2I-Adapter on 'cuda:2', models/pipelines.py:634-697) "
-                                  "is not on this path")
+        _check_xl_stage2(adapter, controlnetpipe)
+        return _final_image_xl(processor, controlnetpipe, overall_prompt, overall_negative_prompt, height, width, bg_seed, inp_mask, input_img, adapter,
+                               latents_all, num_inference_steps, frozen_steps, guidance_scale)
     unet = _own_unet(adapter, "final_image_generation")
     from .controlnet import ControlNetModel
     controlnet = controlnetpipe.controlnet

@@ -185,9 +185,11 @@ class Downsample2D(nn.Module):
         self.conv = nn.Conv2d(channels, channels, 3, stride=2, padding=1)
         self._p = _Packed()
 
-    def run(self, x: _Act):
+    def run(self, x: _Act, res=None):
+        """``res`` (optional, token-major [B*oh*ow, C]): added in the conv's epilogue (a T2I-Adapter feature)"""
         w = self._p.get("w", [self.conv.weight], lambda: pack_conv3x3(self.conv.weight.detach()))
-        out = ops.conv3x3(x.t, w, x.b, x.h, x.w, x.c, stride=2, bias=self.conv.bias)
+        kw = {} if res is None else dict(res=res)
+        out = ops.conv3x3(x.t, w, x.b, x.h, x.w, x.c, stride=2, bias=self.conv.bias, **kw)
         return _Act(out, x.b, (x.h - 1) // 2 + 1, (x.w - 1) // 2 + 1, x.c)
 
 
@@ -644,6 +646,25 @@ class UNet2DConditionModel(nn.Module):
         e_tok = ops.transpose(e, act.b, act.c, act.hw).reshape(act.b * act.hw, act.c)
         return _Act(ops.add(act.t, e_tok), act.b, act.h, act.w, act.c)
 
+    @staticmethod
+    def _same_geometry(act: _Act, extra):
+        if isinstance(extra, _Act):
+            return (extra.b, extra.h, extra.w, extra.c) == (act.b, act.h, act.w, act.c)
+        return tuple(extra.shape) == (act.b, act.c, act.h, act.w)
+
+    def _token_major(self, act: _Act, extra):
+        """a T2I-Adapter feature as a token-major [B*h*w, C] tensor of ``act``'s geometry (NCHW tensors are transposed once)"""
+        if not self._same_geometry(act, extra):
+            got = (extra.b, extra.c, extra.h, extra.w) if isinstance(extra, _Act) else tuple(extra.shape)
+            raise ValueError(f"T2I-Adapter feature shape {got} does not match the UNet activation {(act.b, act.c, act.h, act.w)}")
+        if isinstance(extra, _Act):
+            return extra.t
+        e = extra.to(act.t.dtype).contiguous()
+        return ops.transpose(e, act.b, act.c, act.hw).reshape(act.b * act.hw, act.c)
+
+    def _adapter_add(self, act: _Act, extra):
+        return _Act(ops.add(act.t, self._token_major(act, extra)), act.b, act.h, act.w, act.c)
+
     def forward(self, sample, timestep, encoder_hidden_states, class_labels=None, timestep_cond=None, attention_mask=None,
                 cross_attention_kwargs=None, added_cond_kwargs=None, down_block_additional_residuals=None,
                 mid_block_additional_residual=None, encoder_attention_mask=None, return_dict=True, out_dtype=None, time_proj=None):
@@ -675,23 +696,39 @@ class UNet2DConditionModel(nn.Module):
         x = _Act(ops.conv_in(sample.contiguous(), w_in, self.conv_in.bias, cfg.block_out_channels[0], dt), B, H, W,
                  cfg.block_out_channels[0])
 
+        is_controlnet = mid_block_additional_residual is not None and down_block_additional_residuals is not None
+        is_adapter = mid_block_additional_residual is None and down_block_additional_residuals is not None
+        # T2I-Adapter features (ip_adapter/unet_2d_condition.py:1012-1075, unet_2d_blocks.py:1104-1108), consumed in order: a cross-attention
+        # down block adds the next one to the output of its LAST (resnet, attention) pair, before the skip and the downsampler; a plain down block
+        # adds it after the block (in the downsampler conv's residual slot when it has one), so its last skip carries it too; after the mid block
+        # the next one is added when its shape matches.  NCHW tensors (diffusers surface) or token-major ``_Act``s (DenoiseEngine.set_adapter).
+        feats = list(down_block_additional_residuals) if is_adapter else []
         res = [x]
         for i, blk in enumerate(self.down_blocks):
+            cross_feat = feats.pop(0) if blk.has_cross_attention and feats else None
+            last = len(blk.resnets) - 1
             for j, resnet in enumerate(blk.resnets):
                 x = resnet.run(x, None, tproj)
                 if blk.has_cross_attention:
                     if track_keys:
                         ca_kwargs["attn_key"] = ["down", i, j]
                     x = blk.attentions[j].run(x, enc, ca_kwargs)
+                    if j == last and cross_feat is not None:
+                        x = self._adapter_add(x, cross_feat)
                 res.append(x)
+            plain_feat = feats.pop(0) if not blk.has_cross_attention and feats else None
             if blk.downsamplers is not None:
-                x = blk.downsamplers[0].run(x)
+                ds = blk.downsamplers[0]
+                if plain_feat is not None:
+                    out_geom = _Act(x.t, x.b, (x.h - 1) // 2 + 1, (x.w - 1) // 2 + 1, x.c)        # the downsampler output's geometry (t: dtype only)
+                    x = ds.run(x, res=self._token_major(out_geom, plain_feat))
+                else:
+                    x = ds.run(x)
                 res.append(x)
+            elif plain_feat is not None:
+                x = self._adapter_add(x, plain_feat)
+                res[-1] = x
 
-        is_controlnet = mid_block_additional_residual is not None and down_block_additional_residuals is not None
-        is_adapter = mid_block_additional_residual is None and down_block_additional_residuals is not None
-        if is_adapter:
-            raise NotImplementedError("T2I-Adapter residuals are not on the TheaterGen hot path (SD-1.5 flow uses ControlNet)")
         if is_controlnet:                                            # models/unet_2d_condition.py:938-946
             if len(down_block_additional_residuals) != len(res):
                 raise ValueError("down_block_additional_residuals length mismatch")
@@ -702,6 +739,8 @@ class UNet2DConditionModel(nn.Module):
             ca_kwargs["attn_key"] = ["mid", 0, 0]
         x = self.mid_block.attentions[0].run(x, enc, ca_kwargs)
         x = self.mid_block.resnets[1].run(x, None, tproj)
+        if feats and self._same_geometry(x, feats[0]):
+            x = self._adapter_add(x, feats.pop(0))
         if mid_block_additional_residual is not None:
             x = self._residual(x, mid_block_additional_residual)
 

@@ -354,3 +354,28 @@ def random_vae_state_dict(cfg, seed=0, dtype=torch.float32):
     shapes = OrderedDict(vae_encoder_param_shapes(cfg))
     shapes.update(vae_decoder_param_shapes(cfg))
     return _fill(shapes, seed, dtype)
+
+
+def t2i_adapter_param_shapes(in_channels=3, channels=(320, 640, 1280, 1280), num_res_blocks=2, downscale_factor=16):
+    """diffusers ``T2IAdapter(adapter_type="full_adapter_xl")`` parameter names (``adapter.`` prefix), in module order."""
+    s = OrderedDict()
+    s["adapter.conv_in.weight"] = (channels[0], in_channels * downscale_factor ** 2, 3, 3)
+    s["adapter.conv_in.bias"] = (channels[0],)
+    ins = (channels[0], channels[0], channels[1], channels[3])
+    outs = (channels[0], channels[1], channels[2], channels[3])
+    for k in range(4):
+        p = f"adapter.body.{k}"
+        if ins[k] != outs[k]:
+            s[p + ".in_conv.weight"] = (outs[k], ins[k], 1, 1)
+            s[p + ".in_conv.bias"] = (outs[k],)
+        for j in range(num_res_blocks):
+            s[f"{p}.resnets.{j}.block1.weight"] = (outs[k], outs[k], 3, 3)
+            s[f"{p}.resnets.{j}.block1.bias"] = (outs[k],)
+            s[f"{p}.resnets.{j}.block2.weight"] = (outs[k], outs[k], 1, 1)
+            s[f"{p}.resnets.{j}.block2.bias"] = (outs[k],)
+    return s
+
+
+def random_t2i_adapter_state_dict(seed=0, dtype=torch.float32, **kw):
+    """Seeded init like ``random_unet_state_dict`` (uniform +-1/sqrt(fan_in)); ``kw`` = the ``T2IAdapter`` constructor arguments."""
+    return _fill(t2i_adapter_param_shapes(**kw), seed, dtype)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — 512 px, 50-step character images / second on synthetic CMIGBench 4-turn stories (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   # N = 1
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   # N = 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                    # one rank per GPU over RCCL
 
@@ -12,11 +12,15 @@ CFG/DDIM step epilogue.  Inputs (latents, embeddings) are resident in HBM before
 scaling: every rank denoises its own dialogue per step (no data-path collective); RCCL only broadcasts the
 shared conditioning once and all-gathers the final latents of each step.  Rank 0 prints ONE JSON line.
 
-Extra legs on rank 0 at N = 1 (outside the timed region):
-  roofline     — per-launch HIP-event timing of the dominant kernel family (MFMA GEMM / implicit-GEMM conv),
-                 algorithmic FLOPs (2*M*N*K per launch) / measured time vs the 2.5 PFLOP/s dense bf16 MFMA peak
-  cpu_baseline — the CPU oracle (fp32 PyTorch restatement of the reference path, `oracle/`) timed on the host
-                 cores for a bounded sample (CFG UNet calls), converted to char images / s
+A plain run sets up, warms up, times the steps, writes --dump-outputs if given and prints the line.  With --full,
+rank 0 at N = 1 then runs extra legs outside the timed region (--no-roofline / --no-cpu-baseline / --no-other-configs
+drop one of them):
+  roofline      — per-launch HIP-event timing of the dominant kernel family (MFMA GEMM / implicit-GEMM conv),
+                  algorithmic FLOPs (2*M*N*K per launch) / measured time vs the 2.5 PFLOP/s dense bf16 MFMA peak
+  cpu_baseline  — the CPU oracle (fp32 PyTorch restatement of the reference path, `oracle/`) timed on the host
+                  cores for a bounded sample (CFG UNet calls), converted to char images / s
+  other_configs — short runs of BASELINE.json configs[3] / configs[4] (--plan sd21 / sdxl) and the drop-in
+                  char-batch-1 loops
 """
 import argparse
 import json
@@ -58,13 +62,16 @@ def parse():
     ap.add_argument("--plan", default="sd15", choices=["sd15", "sd21", "sdxl"],
                     help="sd15 = the north-star line (BASELINE.json configs[1]); sd21 = configs[3] (768px editing step with 4-box "
                          "guidance); sdxl = configs[4] (1024px, IP-Adapter-Plus, use --dtype fp16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the extra legs on rank 0 at N = 1 (outside the timed region): roofline, cpu_baseline "
+                         "and other_configs.  Off by default: a plain run does only what its headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short configs[3] (SD-2.1 768px editing step) / configs[4] (SDXL 1024px) legs of the default line")
+                    help="with --full: skip the short configs[3] (SD-2.1 768px editing step) / configs[4] (SDXL 1024px) legs")
     ap.add_argument("--cpu-calls", type=int, default=3)
     ap.add_argument("--cpu-loop-steps", type=int, default=0,
-                    help="also run BASELINE.json configs[0] as an actual loop on the CPU oracle: SD-1.5 512x512, ONE character box, this "
+                    help="with --full: also run BASELINE.json configs[0] as an actual loop on the CPU oracle: SD-1.5 512x512, ONE character box, this "
                          "many DDIM steps (20 = the config; ~100 s at 64 threads), latents by the reference recipe; recorded as "
                          "cpu_baseline.config1_loop next to the bounded-sample extrapolation")
     ap.add_argument("--with-vae", action="store_true",
@@ -899,7 +906,8 @@ def main():
         result.pop("whole_job_tflops"); result.pop("whole_job_mfma_frac")
     if sampler is not None:
         result.update(sampler.summary())
-    if rank == 0 and world == 1 and not args.stage2 and not args.with_vae:
+    legs = args.full and rank == 0 and world == 1 and not args.stage2 and not args.with_vae
+    if legs:
         if not args.no_roofline:
             result["roofline"] = roofline_leg(unet, engine)
             # flat scalars the driver's record keeps: the granted clock / power of THIS run and the whole-job fractions
@@ -917,9 +925,9 @@ def main():
                 result["whole_job_mfma_frac_executed"] = round(ex / elapsed / 1e12 / MFMA_PEAK_TFLOPS, 4)
         if not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline_leg(cfg, sd, dtype, args.cpu_calls, args.ddim_steps, args.cpu_loop_steps)
-    if rank == 0 and world == 1 and not args.stage2 and not args.with_vae and not args.no_other_configs:
-        # BASELINE.json configs[3] / configs[4], short runs of the same code as --plan sd21 / --plan sdxl, folded into THIS line
-        # so that the driver's one bench call records them (they are parity-test configurations, not the metric)
+    if legs and not args.no_other_configs:
+        # BASELINE.json configs[3] / configs[4], short runs of the same code as --plan sd21 / --plan sdxl, folded into the --full line
+        # so that one bench call records them (they are parity-test configurations, not the metric)
         del engines, engine, unet, adapter, prepared
         import gc
         gc.collect()

@@ -6,9 +6,9 @@
 # Summaries are written by scripts/r2_profiles_summary.py into profiles/.
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r2prof; mkdir -p $O; cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --steps 1 --warmup 1 --ddim-steps 10 --no-cpu-baseline --no-roofline"
+BENCH="python $R/bench.py --full --steps 1 --warmup 1 --ddim-steps 10 --no-cpu-baseline --no-roofline"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $BENCH > $O/stats.log 2>&1
-BENCH3="python $R/bench.py --steps 1 --warmup 0 --ddim-steps 3 --no-cpu-baseline --no-roofline"
+BENCH3="python $R/bench.py --full --steps 1 --warmup 0 --ddim-steps 3 --no-cpu-baseline --no-roofline"
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/$c -- $BENCH3 > $O/$c.log 2>&1
 done

@@ -7,4 +7,4 @@ python scripts/dev_boundary.py > $O/boundary.txt 2>&1; TG_CONV_IN_MFMA=0 TG_CONV
 timeout 2700 python -m pytest tests -m gpu -q > $O/gpu_tests.txt 2>&1; tail -3 $O/gpu_tests.txt
 bash scripts/r5_profiles.sh > $O/profiles.log 2>&1; tail -45 $O/profiles.log
 cd $R; cp gpurun_out/r5prof_out/*.json gpurun_out/r5prof_out/*.txt profiles/ 2>/dev/null
-timeout 900 python bench.py > $O/bench_line.json 2> $O/bench.err; head -c 2500 $O/bench_line.json; echo
+timeout 900 python bench.py --full > $O/bench_line.json 2> $O/bench.err; head -c 2500 $O/bench_line.json; echo

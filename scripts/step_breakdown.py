@@ -5,7 +5,7 @@ launch carries its (M, N, K)).
 
     cd /tmp && export TMPDIR=/tmp
     TG_DUMP_RECS=$O/recs.json rocprofv3 --kernel-trace --output-format csv -d $O/trace -- \
-        python bench.py --steps 1 --warmup 1 --ddim-steps 10 --no-cpu-baseline --no-other-configs
+        python bench.py --full --steps 1 --warmup 1 --ddim-steps 10 --no-cpu-baseline --no-other-configs
     python scripts/step_breakdown.py $O/trace $O/recs.json > profiles/rN_step_breakdown.txt
 
 A step = the kernels from one `conv_in_fast_kernel` launch up to the next one; the step reported is the median-duration one among the

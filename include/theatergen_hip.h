@@ -162,6 +162,23 @@ int tg_gemm_plan(const tg_gemm_desc* d, int32_t* tile_m, int32_t* tile_n, int32_
  * of 64-pixel blocks per batch item (the `nblk` of tg_groupnorm_from_partials).  0: it cannot (ask before setting out_gn_partials). */
 int tg_gemm_gn_partial_blocks(const tg_gemm_desc* d);
 
+/* Upsample2D (nearest x2, then conv3x3 pad 1; models/unet_2d_blocks.py:620-622) with the upsampling FOLDED INTO THE WEIGHTS: the nine taps of output pixel
+ * (2i + py, 2j + px) touch only a 2 x 2 block of input pixels, so every parity class cls = 2 py + px is a 2 x 2-tap conv on the low-resolution grid — 4/9 of
+ * tg_gemm's multiply-adds for the same layer.  The descriptor is tg_gemm's: mode 1, upsample 1, stride 1, one source (a1 NULL) of c0 channels (c0 % 64 == 0),
+ * batch / in_h / in_w / out_h = 2 in_h / out_w = 2 in_w, M = batch * out_h * out_w, K = 16 * c0, and
+ *     w = Wf [4][N][4 * c0] in the storage dtype (theatergen_amd.weights_pack.pack_conv3x3_up2): class-major, within a class tap-major (ty, tx, c);
+ *         Wf[cls][n][ty, tx, c] = sum of W[n, c, ky, kx] over ky in rows(py, ty), kx in rows(px, tx), summed in fp32 and rounded once, with
+ *         rows(0, 0) = {0}, rows(0, 1) = {1, 2}, rows(1, 0) = {0, 1}, rows(1, 1) = {2};
+ *     out[((b * out_h + 2i + py) * out_w + 2j + px) * ldc + n] = bias[n] + sum over ty, tx, c of Wf[cls][n][ty, tx, c] * X[b, i + py + ty - 1, j + px + tx - 1, c],
+ *         X zero outside the image; fp32 accumulation, one rounding.
+ * Bias is the only epilogue term: a descriptor with bvec / res / act / geglu / n_split / out_scale != 1 / a_coef / ln_* / out_gn_partials / force_* is refused
+ * (TG_ERR_UNSUPPORTED), as is a geometry the kernel does not take: in_w in {16, 32, 64} with in_h a multiple of 128 / in_w, or in_h = in_w = 8, and
+ * batch * in_h * in_w a multiple of 128; N % 8 == 0, ldc % 8 == 0, out / bias 16-byte aligned, every operand under 2^31 bytes.  A malformed descriptor
+ * (second source, K != 16 * c0, inconsistent sizes, misaligned a0 / w) is TG_ERR_ARG.  All checks run on the host before any launch; no workspace, no K split.
+ * tg_conv_up2_eligible: 1 when tg_conv_up2 takes the descriptor, else 0 (the caller then runs the unfolded layer through tg_gemm, W = [N, 9 * c0]). */
+int tg_conv_up2_eligible(const tg_gemm_desc* d);
+int tg_conv_up2(const tg_gemm_desc* d, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fused flash-style attention with up to two independently-normalised K/V segments:
  *     O = softmax(s Q K0^T) V0  +  w1 * softmax(s Q K1^T) V1

@@ -146,6 +146,8 @@ SIGNATURES = {
     "tg_groupnorm_coef": (i32, [i32, vp, vp, i32, i32, i32, i64, i32, f32, vp, vp, vp, vp, vp]),
     "tg_groupnorm_from_partials": (i32, [i32, vp, i32, i32, i64, i32, f32, vp, vp, i32, vp, vp, vp, i32, vp]),
     "tg_gemm_gn_partial_blocks": (i32, [C.POINTER(GemmDesc)]),
+    "tg_conv_up2_eligible": (i32, [C.POINTER(GemmDesc)]),
+    "tg_conv_up2": (i32, [C.POINTER(GemmDesc), vp]),
     "tg_geglu": (i32, [i32, vp, i64, i64, vp, vp]),
     "tg_act": (i32, [i32, vp, i64, i32, vp, vp]),
     "tg_add": (i32, [i32, vp, vp, i64, vp, vp]),

@@ -18,13 +18,20 @@ namespace {
 // two-source layers (93 vs 86 us): a K-step takes ~0.9-1.0 us whatever the structure; removed.  profiles/r5_t160_findings.md.)
 // UPS = true: the same for Upsample2D (nearest x2 then conv3x3): WI is the OUTPUT width, the slab holds the
 // (TH/2 + 2) x (WI/2 + 2) INPUT pixels the block's upsampled window maps to (input pixel = upsampled coordinate >> 1).
-template <typename T, int WI, bool UPS>
+// FOLD = true (tg_conv_up2): Upsample2D with the nearest x2 FOLDED INTO THE WEIGHTS.  The nine taps of output pixel (2i + py, 2j + px) touch only the
+// 2 x 2 input pixels (i + py + ty - 1, j + px + tx - 1), so each parity class cls = 2 py + px is a 2 x 2-tap conv on the LOW-RESOLUTION grid with
+// weights that are sums of the original taps (weights_pack.pack_conv3x3_up2: [4][N][4 C], tap-major (ty, tx, c)): 4/9 of the MFMAs.  WI is the
+// low-resolution width, the block = 128 low-resolution pixels of ONE class x 128 channels, the slab is the plain (UPS = false) geometry, the K loop runs
+// 4 taps per channel chunk, and the epilogue scatters local row (img, i, j) to token (img 2H + 2i + py) 2W + 2j + px.  No K split, bias only.
+template <typename T, int WI, bool UPS, bool FOLD = false>
 __global__ __launch_bounds__(256) void conv_halo_kernel(GemmParams p) {
   constexpr int BM = 128, BN = 128, NW = 4, TM = 2, TN = 2, WAVES_N = 2;
   // WI = 8 (the 8x8 level): a block's 128 pixels are TWO whole 8x8 images; their two 10x10 padded windows are stacked
   // in the slab (20 slab rows of width 10), everything else is unchanged
   constexpr bool MULTI = WI == 8;
   static_assert(!(MULTI && UPS), "no upsample variant at width 8");
+  static_assert(!(FOLD && UPS), "the folded instance runs on the low-resolution grid");
+  constexpr int NT = FOLD ? 4 : 9;                    // taps = K-steps per channel chunk
   constexpr int TH = BM / WI, WIN = UPS ? WI / 2 : WI, SW = WIN + 2, SROWS = MULTI ? 20 : (UPS ? TH / 2 + 2 : TH + 2);
   constexpr int SLAB = SROWS * SW, NI = (SLAB + 7) / 8, SJ = (NI + NW - 1) / NW;
   constexpr int WJ = BN / (8 * NW);
@@ -45,8 +52,11 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(GemmParams p) {
   const int wave_m = wave / WAVES_N;
   const int wave_n = wave % WAVES_N;
   int lbid, split = 0, part = -1;     // same work-item scheme as gemm_glds_kernel; the K split runs over channel chunks
+  int cls = 0;                        // FOLD: output parity class 2 py + px of this work item
   if ((int)blockIdx.x < p.full_tiles) {
     lbid = xcd_chunked_block_id(blockIdx.x, p.full_tiles);
+    // the four classes of one (row tile, column tile) are neighbours in the walk: same XCD, same time, one input window in L2
+    if (FOLD) { cls = lbid & 3; lbid >>= 2; }
   } else {
     const int j = (int)blockIdx.x - p.full_tiles;
     lbid = p.full_tiles + j / p.tail_s;
@@ -70,7 +80,8 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(GemmParams p) {
 
   const T* A0 = reinterpret_cast<const T*>(p.a0);
   const T* A1 = reinterpret_cast<const T*>(p.a1);
-  const T* Wp = reinterpret_cast<const T*>(p.w);
+  const T* Wp = reinterpret_cast<const T*>(p.w) + (FOLD ? (long)cls * p.N * p.K : 0L);   // FOLD: p.K = 4 C, the row pitch inside one class
+  const int cpy = cls >> 1, cpx = cls & 1;
   const T* zero = reinterpret_cast<const T*>(tg_zero_page);
   const int ctot = p.c0 + p.c1;
   const int nchunks = ctot / BK;
@@ -163,14 +174,14 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(GemmParams p) {
   int c_end = part >= 0 ? c_begin + p.kt_per_split : nchunks;
   if (c_end > nchunks) c_end = nchunks;
 
-  const int nkt = (c_end - c_begin) * 9;
+  const int nkt = (c_end - c_begin) * NT;
   int icc = c_begin, itap = 0;                         // (chunk, tap) of the next W tile to request
   issue_slab(c_begin);
 #pragma unroll
   for (int s_ = 0; s_ < WD; ++s_) {
     if (s_ < nkt) {
       issue_w(icc, itap, s_);
-      if (++itap == 9) { itap = 0; ++icc; }
+      if (++itap == NT) { itap = 0; ++icc; }
     }
   }
   if (WD == 2 && nkt >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WJ) : "memory");
@@ -180,7 +191,8 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(GemmParams p) {
   int cc = c_begin, tap = 0;
   int buf = 0;
   for (int kt = 0; kt < nkt; ++kt) {
-    const int ky = tap / 3, kx = tap - ky * 3;
+    int ky = tap / 3, kx = tap - ky * 3;
+    if (FOLD) { ky = cpy + (tap >> 1); kx = cpx + (tap & 1); }   // tap (ty, tx) of class (py, px) reads slab row (y + py + ty) * SW + x + px + tx
     const T* bw = sW + buf * BN * BK + (wave_n * TN * 32 + l31) * BK;
     V8 xf[BK / 16][TM], wf[BK / 16][TN];
 #pragma unroll
@@ -200,11 +212,15 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(GemmParams p) {
     }
     __builtin_amdgcn_sched_barrier(0);
     int ncc = cc, ntap = tap + 1;
-    if (ntap == 9) { ntap = 0; ncc = cc + 1; }
+    if (ntap == NT) { ntap = 0; ncc = cc + 1; }
     if (kt + 1 < nkt) {
       if (ntap == 0) {
-        // the next K-step starts a new channel chunk: every wave must have its tap-8 fragments in registers before
-        // the slab is overwritten; the slab DMA then overlaps this step's 16 MFMAs
+        // the next K-step starts a new channel chunk: every wave must have its LAST-tap fragments (tap 8; FOLD: tap 3) in registers before
+        // the slab is overwritten; the slab DMA then overlaps this step's 16 MFMAs.  Nothing here depends on the number of taps per chunk:
+        // write-after-read — the fragments of the chunk's earlier taps were consumed by their own steps' MFMAs, which every wave finished
+        // before that step's closing barrier, and this step's reads are covered by the lgkmcnt(0) + barrier below; read-after-write — the
+        // slab request is OLDER than this step's W request, so the closing vmcnt(WJ) (or vmcnt(0)) + barrier of this step sees it landed
+        // before the next step's first fragment read.  With FOLD the extra barrier fires every 4th step instead of every 9th.
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         issue_slab(ncc);
@@ -214,7 +230,7 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(GemmParams p) {
       int nb = buf + WD;
       if (nb >= WST) nb -= WST;
       issue_w(icc, itap, nb);
-      if (++itap == 9) { itap = 0; ++icc; }
+      if (++itap == NT) { itap = 0; ++icc; }
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -234,16 +250,67 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(GemmParams p) {
     buf = buf + 1 == WST ? 0 : buf + 1;
   }
 
-  epilogue_tile_lds<T, TM, TN, 0>(p, acc, m0 + wave_m * TM * 32, n0 + wave_n * TN * 32, lane,
-                                 reinterpret_cast<float*>(smem) + wave * (32 * (TN * 32 + 4)), part, m0, n0);
+  if constexpr (FOLD) {
+    // Mapped-row LDS epilogue (precedent: the slab conv's patch rows, PR / patch_token in tg_gemm_common.h).  Same bounce as epilogue_rows_lds —
+    // the operand stages are dead after the K loop's last barrier, each wave owns 32 x 68 floats — and the same fp32 expression (acc + bias, one
+    // rounding; the host admits bias only: no residual, per-batch vector, activation, scale, n_split or GroupNorm partials), so an exact-arithmetic
+    // input gives the unfolded kernel's bits.  Lane = (row r0 + 8 it, 8-channel piece c): 16-byte stores, 128 contiguous bytes per token row.
+    constexpr int RS = TN * 32 + 4;
+    float* scr = reinterpret_cast<float*>(smem) + wave * (32 * RS);
+    const int c8 = lane & 7, r0 = lane >> 3;
+    const long n = n0 + wave_n * TN * 32 + c8 * 8;
+    const bool n_ok = n < p.N;
+    float bias_f[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bias_f[e] = 0.f;
+    if (p.bias != nullptr) {
+      const V8 b8 = *reinterpret_cast<const V8*>(reinterpret_cast<const T*>(p.bias) + (n_ok ? n : 0));
+#pragma unroll
+      for (int e = 0; e < 8; ++e) bias_f[e] = to_f32<T>(b8[e]);
+    }
+    T* outp = reinterpret_cast<T*>(p.out);
+    const int hw = H * WI;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          f32x4 o = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+          *reinterpret_cast<f32x4*>(scr + l31 * RS + 32 * j + 8 * g + 4 * hi) = o;
+        }
+      __builtin_amdgcn_wave_barrier();
+      f32x4 lo[4], hi4[4];
+#pragma unroll
+      for (int it = 0; it < 4; ++it) {
+        lo[it] = *reinterpret_cast<const f32x4*>(scr + (it * 8 + r0) * RS + c8 * 8);
+        hi4[it] = *reinterpret_cast<const f32x4*>(scr + (it * 8 + r0) * RS + c8 * 8 + 4);
+      }
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int it = 0; it < 4; ++it) {
+        const int ml = (int)m0 + wave_m * TM * 32 + i * 32 + it * 8 + r0;     // low-resolution pixel (img, yi, xj)
+        const int im = ml / hw, rem = ml - im * hw;
+        const int yi = rem / WI, xj = rem - yi * WI;
+        const long tok = ((long)im * 2 * H + 2 * yi + cpy) * (2 * WI) + 2 * xj + cpx;
+        V8 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { o[e] = from_f32<T>(lo[it][e] + bias_f[e]); o[4 + e] = from_f32<T>(hi4[it][e] + bias_f[4 + e]); }
+        if (ml < p.M && n_ok) *reinterpret_cast<V8*>(outp + tok * p.ldc + n) = o;
+      }
+    }
+  } else {
+    epilogue_tile_lds<T, TM, TN, 0>(p, acc, m0 + wave_m * TM * 32, n0 + wave_n * TN * 32, lane,
+                                   reinterpret_cast<float*>(smem) + wave * (32 * (TN * 32 + 4)), part, m0, n0);
+  }
 }
 
-template <typename T, int WI, bool UPS>
+template <typename T, int WI, bool UPS, bool FOLD = false>
 int launch_halo(const GemmParams& p, int grid, hipStream_t st) {
   constexpr int TH = 128 / WI, SLAB = WI == 8 ? 200 : (UPS ? (TH / 2 + 2) * (WI / 2 + 2) : (TH + 2) * (WI + 2)), NI = (SLAB + 7) / 8;
   const int wst = ((size_t)NI * 8 * BK + 3 * 128 * BK) * sizeof(T) <= 80 * 1024 ? 3 : 2;
   const size_t lds = ((size_t)NI * 8 * BK + wst * 128 * BK) * sizeof(T);
-  auto k = conv_halo_kernel<T, WI, UPS>;
+  auto k = conv_halo_kernel<T, WI, UPS, FOLD>;
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   (void)attr;
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, st, p);
@@ -264,7 +331,72 @@ int dispatch_halo(const tg_gemm_desc* d, const GemmParams& p, int grid, hipStrea
   return launch_halo<T, 16, false>(p, grid, st);
 }
 
+template <typename T>
+int dispatch_up2(const tg_gemm_desc* d, const GemmParams& p, int grid, hipStream_t st) {
+  if (d->in_w == 64) return launch_halo<T, 64, false, true>(p, grid, st);
+  if (d->in_w == 32) return launch_halo<T, 32, false, true>(p, grid, st);
+  if (d->in_w == 16) return launch_halo<T, 16, false, true>(p, grid, st);
+  return launch_halo<T, 8, false, true>(p, grid, st);
+}
+
+// tg_conv_up2's host-side contract (include/theatergen_hip.h); every check runs before any launch
+int up2_validate(const tg_gemm_desc* d) {
+  TG_CHECK(d != nullptr, TG_ERR_ARG, "tg_conv_up2: null descriptor");
+  TG_CHECK(d->dtype == TG_BF16 || d->dtype == TG_F16, TG_ERR_ARG, "tg_conv_up2: bad dtype %d", d->dtype);
+  TG_CHECK(d->a0 && d->w && d->out, TG_ERR_ARG, "tg_conv_up2: null a0/w/out");
+  TG_CHECK((reinterpret_cast<uintptr_t>(d->a0) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->w) & 15) == 0, TG_ERR_ARG,
+           "tg_conv_up2: a0 / w must be 16-byte aligned (a0=%p w=%p)", d->a0, d->w);
+  TG_CHECK(d->mode == 1 && d->upsample == 1 && d->stride == 1 && d->pad_mode == 0, TG_ERR_ARG,
+           "tg_conv_up2: the descriptor must be mode 1, upsample 1, stride 1, pad_mode 0");
+  TG_CHECK(d->a1 == nullptr, TG_ERR_ARG, "tg_conv_up2: single source only (a1 must be NULL)");
+  TG_CHECK(d->batch > 0 && d->in_h > 0 && d->in_w > 0 && d->c0 > 0 && d->N > 0, TG_ERR_ARG, "tg_conv_up2: empty problem");
+  TG_CHECK(d->K == 16L * d->c0, TG_ERR_ARG, "tg_conv_up2: K must be 16*c0 (four classes of four folded taps), got K=%lld c0=%d", (long long)d->K, d->c0);
+  TG_CHECK(d->out_h == 2 * d->in_h && d->out_w == 2 * d->in_w, TG_ERR_ARG, "tg_conv_up2: out %dx%d inconsistent with in %dx%d",
+           d->out_h, d->out_w, d->in_h, d->in_w);
+  TG_CHECK(d->M == (int64_t)d->batch * d->out_h * d->out_w, TG_ERR_ARG, "tg_conv_up2: M != batch*out_h*out_w");
+  TG_CHECK(d->bvec == nullptr && d->res == nullptr && d->act == TG_ACT_NONE && !d->geglu && d->n_split <= 0 && d->out_scale == 1.0f &&
+           d->a_coef == nullptr && d->ln_u == nullptr && d->ln_v == nullptr && d->ln_rows == nullptr && d->out_gn_partials == nullptr &&
+           d->force_split_k <= 1 && d->force_tile == 0 && d->lda <= 0 && d->ldw <= 0 && d->a_rows_per_batch <= 0,
+           TG_ERR_UNSUPPORTED, "tg_conv_up2: bias is the only epilogue term (no residual / per-batch vector / activation / scale / split / fold / forced plan)");
+  TG_CHECK(d->c0 % BK == 0, TG_ERR_UNSUPPORTED, "tg_conv_up2: c0 %% 64 required (c0=%d)", d->c0);
+  const long mlo = (long)d->batch * d->in_h * d->in_w;
+  bool geo = mlo % 128 == 0;
+  if (d->in_w == 8) geo = geo && d->in_h == 8;                                      // two whole 8 x 8 images per block
+  else geo = geo && (d->in_w == 16 || d->in_w == 32 || d->in_w == 64) && d->in_h % (128 / d->in_w) == 0;   // whole image rows, blocks inside one image
+  TG_CHECK(geo, TG_ERR_UNSUPPORTED, "tg_conv_up2: low-resolution map %dx%d x batch %d is not 128-pixel blocks of whole rows at width 8 / 16 / 32 / 64",
+           d->in_h, d->in_w, d->batch);
+  TG_CHECK(d->N % 8 == 0 && d->ldc % 8 == 0 && d->ldc >= d->N && (reinterpret_cast<uintptr_t>(d->out) & 15) == 0 &&
+           (reinterpret_cast<uintptr_t>(d->bias) & 15) == 0, TG_ERR_UNSUPPORTED, "tg_conv_up2: N %% 8, ldc %% 8 and 16-byte aligned out / bias required");
+  // 32-bit byte offsets of the LDS-DMA requests and int pixel / token indices in the kernel
+  const long esz = 2;
+  TG_CHECK(mlo * d->c0 * esz < (1L << 31) && d->M * d->ldc * esz < (1L << 31) && d->N * 4L * d->c0 * esz < (1L << 31), TG_ERR_UNSUPPORTED,
+           "tg_conv_up2: an operand extent reaches 2^31 bytes");
+  return TG_OK;
+}
+
 }  // namespace
+
+extern "C" int tg_conv_up2_eligible(const tg_gemm_desc* d) { return up2_validate(d) == TG_OK ? 1 : 0; }
+
+extern "C" int tg_conv_up2(const tg_gemm_desc* d, void* stream) {
+  const int rc = up2_validate(d);
+  if (rc != TG_OK) return rc;
+  GemmParams p{};
+  p.a0 = d->a0; p.c0 = d->c0;
+  p.in_h = d->in_h; p.in_w = d->in_w; p.out_h = d->out_h; p.out_w = d->out_w; p.stride = 1; p.upsample = 1; p.pad_lo = 1;
+  p.w = d->w;
+  p.M = (long)d->batch * d->in_h * d->in_w;        // the kernel's rows are LOW-RESOLUTION pixels
+  p.N = d->N;
+  p.K = 4L * d->c0;                                // weight row pitch inside one parity class
+  p.bias = d->bias; p.rows_per_batch = p.M; p.out_scale = 1.0f;
+  p.out = d->out; p.ldc = d->ldc;
+  p.tiles_n = (int)((d->N + 127) / 128);
+  p.full_tiles = (int)(p.M / 128) * 4 * p.tiles_n; p.tail_s = 1; p.tile_bm = 128; p.tile_bn = 128;
+  p.patch_np = 1; p.epi_lds = 1;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (d->dtype == TG_BF16) return dispatch_up2<bf16_t>(d, p, p.full_tiles, st);
+  return dispatch_up2<f16_t>(d, p, p.full_tiles, st);
+}
 
 // grid = full tiles + tail tiles * K splits (the caller, tg_gemm.hip, owns the plan and launches the split reduce)
 int tg_conv_halo_launch(const tg_gemm_desc* d, const void* params, int grid, void* stream) {

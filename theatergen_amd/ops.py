@@ -397,6 +397,50 @@ def conv3x3(x, w_packed, batch, in_h, in_w, cin, *, x1=None, c1=0, stride=1, ups
                 conv=(batch, in_h, in_w, oh, ow, stride, 1 if upsample else 0), bias=bias, pad_mode=pad_mode, **kw)
 
 
+def _up2_desc(dtype, batch, in_h, in_w, cin, cout):
+    d = GemmDesc()
+    d.dtype = _lib.TG_BF16 if dtype == torch.bfloat16 else _lib.TG_F16
+    d.mode, d.stride, d.upsample = 1, 1, 1
+    d.c0 = int(cin)
+    d.batch, d.in_h, d.in_w, d.out_h, d.out_w = int(batch), int(in_h), int(in_w), 2 * int(in_h), 2 * int(in_w)
+    d.M, d.N, d.K = 4 * int(batch) * int(in_h) * int(in_w), int(cout), 16 * int(cin)
+    d.out_scale = 1.0
+    d.ldc = int(cout)
+    return d
+
+
+_up2_plans = {}
+
+
+def conv_up2_eligible(dtype, batch, in_h, in_w, cin, cout):
+    """True when ``conv_up2`` (tg_conv_up2: the nearest-x2 folded into four 2x2-tap convs) takes this Upsample2D layer with a contiguous output."""
+    key = (dtype, batch, in_h, in_w, cin, cout)
+    hit = _up2_plans.get(key)
+    if hit is None:
+        if dtype not in (torch.bfloat16, torch.float16):
+            return False
+        d = _up2_desc(dtype, batch, in_h, in_w, cin, cout)
+        d.a0 = d.w = d.out = 16                      # eligibility only: pointers are not dereferenced, just non-NULL and aligned
+        hit = _up2_plans[key] = bool(_lib.lib().tg_conv_up2_eligible(C.byref(d)))
+    return hit
+
+
+def conv_up2(x, w_folded, batch, in_h, in_w, cin, bias=None, out=None):
+    """Upsample2D (nearest x2 + conv3x3 pad 1) over token-major x [batch*in_h*in_w, cin] with ``w_folded`` = ``weights_pack.pack_conv3x3_up2``
+    ([4, cout, 4*cin]) -> [batch*2*in_h*2*in_w, cout]; see tg_conv_up2.  Raises where the kernel does not take the layer (no fallback here)."""
+    _need_cuda(x)
+    assert w_folded.dim() == 3 and w_folded.shape[0] == 4 and w_folded.shape[2] == 4 * cin and w_folded.is_contiguous(), tuple(w_folded.shape)
+    assert x.stride(1) == 1 and x.stride(0) == cin and w_folded.dtype == x.dtype
+    N = w_folded.shape[1]
+    d = _up2_desc(x.dtype, batch, in_h, in_w, cin, N)
+    if out is None:
+        out = torch.empty((d.M, N), dtype=x.dtype, device=x.device)
+    d.a0, d.w, d.bias, d.out, d.ldc = _ptr(x), _ptr(w_folded), _ptr(bias), _ptr(out), int(out.stride(0))
+    # algorithmic work of the layer as the caller sees it (the unfolded conv), so TFLOP/s compare with the unfolded kernel's records
+    _profiled(lambda: _lib.check(_lib.lib().tg_conv_up2(C.byref(d), _stream())), "conv_halo_kernel<up2,128x128>", d.M, N, 9 * cin, 2.0 * d.M * N * 9 * cin)
+    return out
+
+
 def attention(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale,
               out, out_ld, out_bs, k1=None, k1_ld=0, k1_bs=0, vt1=None, vt1_ld=0, vt1_bs=0, len1=0, w1=0.0, causal=False, w1_dev=None,
               mask=None):

@@ -31,7 +31,7 @@ from . import rowchain
 from .attention_processor import (tensor_version, Attention, AttnProcessor, CNAttnProcessor, IPAttnProcessor, _cached, front_eligible, fused_cross_block,
                                   ln_weight, self_attention_from_qkv)
 from .config import UNetConfig
-from .weights_pack import pack_conv1x1, pack_conv3x3, pack_geglu, pack_ln_linear, rc_pack_tiles
+from .weights_pack import pack_conv1x1, pack_conv3x3, pack_conv3x3_up2, pack_geglu, pack_ln_linear, rc_pack_tiles
 
 
 class DeviceSchedule:
@@ -193,8 +193,15 @@ class Downsample2D(nn.Module):
         return _Act(out, x.b, (x.h - 1) // 2 + 1, (x.w - 1) // 2 + 1, x.c)
 
 
+# Upsample2D on tg_conv_up2 (nearest x2 folded into the weights: four 2x2-tap convs, 4/9 of the MFMAs) where the kernel takes the layer.  TG_UP_FOLD=0 (dev A/B) = off.
+_UP_FOLD = os.environ.get("TG_UP_FOLD", "1") != "0"
+
+
 class Upsample2D(nn.Module):
-    """nearest x2 folded into the conv3x3 gather (``Upsample2D(use_conv=True)``, unet_2d_blocks.py:620-622)."""
+    """``Upsample2D(use_conv=True)`` (unet_2d_blocks.py:620-622): nearest x2, then conv3x3.  The nine taps of an upsampled pixel touch a 2 x 2 block of
+    input pixels, so where ``tg_conv_up2`` takes the layer (low-resolution width 8 / 16 / 32 / 64 in whole 128-pixel blocks, one source) the
+    upsampling is folded into the WEIGHTS (``pack_conv3x3_up2``: one 2x2-tap conv per output parity class, summed once per weight version in the
+    ``_Packed`` cache like every repack); every other geometry folds it into the conv3x3 gather of ``ops.conv3x3(..., upsample=True)`` as before."""
 
     def __init__(self, channels):
         super().__init__()
@@ -202,6 +209,10 @@ class Upsample2D(nn.Module):
         self._p = _Packed()
 
     def run(self, x: _Act):
+        if _UP_FOLD and ops.conv_up2_eligible(x.t.dtype, x.b, x.h, x.w, x.c, self.conv.out_channels):
+            wf = self._p.get("w_up2", [self.conv.weight], lambda: pack_conv3x3_up2(self.conv.weight.detach()))
+            out = ops.conv_up2(x.t, wf, x.b, x.h, x.w, x.c, bias=self.conv.bias)
+            return _Act(out, x.b, 2 * x.h, 2 * x.w, x.c)
         w = self._p.get("w", [self.conv.weight], lambda: pack_conv3x3(self.conv.weight.detach()))
         out = ops.conv3x3(x.t, w, x.b, x.h, x.w, x.c, upsample=True, bias=self.conv.bias)
         return _Act(out, x.b, 2 * x.h, 2 * x.w, x.c)

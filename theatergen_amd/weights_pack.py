@@ -3,6 +3,7 @@ the HIP kernels read.  Token-major activations want K-contiguous weights:
   Linear  [N, K]            -> unchanged
   Conv1x1 [N, C, 1, 1]      -> [N, C]
   Conv3x3 [N, C, 3, 3]      -> [N, 9*C] tap-major (ky, kx, c)  (implicit-GEMM K order of tg_gemm mode 1)
+  Upsample2D's conv         -> [4, N, 4*C] parity-class-major, folded taps (ty, tx, c)  (tg_conv_up2)
 """
 import torch
 
@@ -11,6 +12,25 @@ def pack_conv3x3(w: torch.Tensor) -> torch.Tensor:
     n, c, kh, kw = w.shape
     assert kh == 3 and kw == 3
     return w.permute(0, 2, 3, 1).reshape(n, 9 * c).contiguous()
+
+
+_UP2_ROWS = (((0,), (1, 2)), ((0, 1), (2,)))      # [parity][folded tap] -> original taps: nearest x2 maps them onto one input row / column
+
+
+def pack_conv3x3_up2(w: torch.Tensor) -> torch.Tensor:
+    """Upsample2D's conv3x3 with the nearest x2 folded in (tg_conv_up2): [N, C, 3, 3] -> [4, N, 4*C] in w's dtype.  Output pixel
+    (2i+py, 2j+px) sees only the 2 x 2 input pixels (i+py+ty-1, j+px+tx-1), ty, tx in {0, 1}; class cls = 2*py + px holds, tap-major
+    (ty, tx, c), the sums of the original taps that land on each of them.  Summed in fp32 (fp64 stays fp64), rounded once."""
+    n, c, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    acc = w.detach().to(torch.float64 if w.dtype == torch.float64 else torch.float32)
+    out = torch.empty(4, n, 2, 2, c, dtype=acc.dtype, device=w.device)
+    for py in range(2):
+        for px in range(2):
+            for ty in range(2):
+                for tx in range(2):
+                    out[2 * py + px, :, ty, tx] = sum(acc[:, :, ky, kx] for ky in _UP2_ROWS[py][ty] for kx in _UP2_ROWS[px][tx])
+    return out.reshape(4, n, 4 * c).to(w.dtype).contiguous()
 
 
 def pack_conv1x1(w: torch.Tensor) -> torch.Tensor:

@@ -223,7 +223,8 @@ int tg_attention(const tg_attn_desc* d, void* stream);
  * (ip_adapter/attention_processor.py:113-219).  Three launches of one kernel (row statistics lse / D, dQ, dK + dV); scores are recomputed from Q / K
  * tiles, nothing n x n exists in memory.  q, k, v, dout, dq, dk, dv: [batch][n][>= heads * head_dim] rows of pitch `ld`, batch stride `bs` (elements);
  * qt, kt, doutt: the TRANSPOSES [batch][heads * head_dim][n] (tg_transpose) with row pitch `t_ld`, batch stride `t_bs`; stats: fp32 scratch
- * [batch][heads][n][2].  P and dS are rounded to the storage dtype where they enter a product (as a materialised implementation stores them).
+ * [batch][heads][n][2].  One `ld` / `bs` serves the seven row-major tensors; columns >= heads * head_dim of a row, rows >= n of a batch item and columns >= n
+ * of a transposed row are never read or written.  P and dS are rounded to the storage dtype where they enter a product (as a materialised implementation stores them).
  * TG_ERR_UNSUPPORTED for other head dims / ragged n: the caller keeps its materialised path. */
 typedef struct {
   int32_t dtype, batch, heads, head_dim, n;
@@ -238,7 +239,7 @@ typedef struct {
 int tg_attention_bwd(const tg_attn_bwd_desc* d, void* stream);
 /* The same for one softmax segment of CROSS-attention (text keys, or the IP-Adapter's image keys: ip_adapter/attention_processor.py:445-529): K / V are
  * constants of the conditioning, so only dQ is produced (statistics + dQ launches), over n_k keys (any count; `kt` = K^T [batch][heads * head_dim][t_ld]
- * zero-padded to a multiple of 8 columns).  `extra` (optional, fp32 [batch][heads][n_q][extra_ld >= n_k]): d loss / d P of a loss that reads the
+ * zero-padded to a multiple of 8 columns: columns [n_k, roundup8(n_k)) are read and must be zero, columns past them are never read).  `extra` (optional, fp32 [batch][heads][n_q][extra_ld >= n_k]): d loss / d P of a loss that reads the
  * probabilities (the guidance loss on the text maps, utils/guidance.py:91-286) — it joins dO V^T before the softmax Jacobian.  `scale`: softmax scale;
  * `ds_scale`: scale x the segment's output weight (the IP scale for the image segment).  dq is written (not accumulated). */
 typedef struct {

@@ -537,6 +537,16 @@ def test_attention_reverse_pass_without_materialised_probabilities(dtype, B, N, 
     l2, mx = (2e-2, 6e-2) if dtype == torch.bfloat16 else (3e-3, 1.5e-2)
     for name, got, ref in (("dQ", dq, rq), ("dK", dk, rk), ("dV", dv, rv)):
         pm.check(got.float().cpu().reshape(B, N, heads, d).permute(0, 2, 1, 3), ref, f"attention_bwd {name} {(B, N, heads, d)} {dtype}", l2, mx)
+    # the fp64 restatement of the C-ABI contract (P and dS rounded where they enter a product), whole tensor and every (item, head, 128-row block)
+    # at the per-launch attention bound: a fault in one ragged tile or one workgroup's block cannot hide in the whole-tensor average
+    from tests import attn_bwd_contract as ab
+    from tests import launch_check as lc
+    a = ab.self_desc(q.to(DEV), k.to(DEV), v.to(DEV), do.to(DEV), None, None, None, None, None, None, None, batch=B, heads=heads, head_dim=d, n=N,
+                     ld=inner, bs=N * inner, t_ld=N, t_bs=inner * N, scale=scale)
+    want = ab.self_reference(a)
+    for name, got in (("dq", dq), ("dk", dk), ("dv", dv)):
+        ab.check(got.reshape(B, N, inner), want[name], heads, f"attention_bwd contract {name} {(B, N, heads, d)} {dtype}",
+                 1.5 * lc.l2_tol(dtype), 1.5 * lc.rel_tol(dtype))
     again = ops.attention_bwd(q.to(DEV), k.to(DEV), v.to(DEV), do.to(DEV), B, N, heads, d, scale)
     assert all(torch.equal(a, b) for a, b in zip((dq, dk, dv), again)), "not deterministic"
 
@@ -594,3 +604,11 @@ def test_cross_attention_reverse_pass_segment(dtype, B, N, L, heads, d, with_ext
     # (the kernel's dS = ds_scale * P o (dP + extra - D): with a segment weight the caller's extra is per unit of weight)
     l2, mx = (2e-2, 6e-2) if dtype == torch.bfloat16 else (3e-3, 1.5e-2)
     pm.check(dq.float().cpu().reshape(B, N, heads, d).permute(0, 2, 1, 3), ref, f"attention_bwd_cross {(B, N, L, heads, d, with_extra)} {dtype}", l2, mx)
+    # the fp64 restatement of the C-ABI contract, whole tensor and every (item, head, 128-row block), at the per-launch attention bound
+    from tests import attn_bwd_contract as ab
+    from tests import launch_check as lc
+    a = ab.cross_desc(q.to(DEV), do.to(DEV), k.to(DEV), v.to(DEV), None, (extra / wgt).to(DEV) if with_extra else None, None, None, batch=B,
+                      heads=heads, head_dim=d, n_q=N, n_k=L, q_ld=inner, q_bs=N * inner, k_ld=inner, k_bs=L * inner, t_ld=(L + 7) // 8 * 8,
+                      t_bs=inner * ((L + 7) // 8 * 8), extra_ld=L, scale=scale, ds_scale=scale * wgt)
+    ab.check(dq.reshape(B, N, inner), ab.cross_reference(a)["dq"], heads, f"attention_bwd_cross contract {(B, N, L, heads, d, with_extra)} {dtype}",
+             1.5 * lc.l2_tol(dtype), 1.5 * lc.rel_tol(dtype))

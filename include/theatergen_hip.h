@@ -253,6 +253,17 @@ typedef struct {
   float scale, ds_scale;
 } tg_attn_bwd_cross_desc;
 int tg_attention_bwd_cross(const tg_attn_bwd_cross_desc* d, void* stream);
+/* The two reverse passes above for WIDE heads, 64 < head_dim <= 160, head_dim % 8 == 0 (SD-1.5's inner levels: d = 80 / 160; csrc/tg_attention_bwd_wide.hip).
+ * Same descriptors, same contract text, same roundings and launch structure (statistics, dQ, and for self-attention dK + dV); tg_attention_bwd_cross_wide keeps
+ * the zero-padded `kt` rule and the `extra` rule.  For head_dim > 96 the output columns of a launch are split over two workgroups, each of which
+ * recomputes the scores over the full head dim; every output element is still written by exactly one lane, no atomics.
+ * Validation is on the host, before any launch; a refused descriptor writes nothing:
+ *   TG_ERR_UNSUPPORTED  head_dim <= 64 (that is tg_attention_bwd / tg_attention_bwd_cross, which in turn keep refusing head_dim > 64), head_dim > 160,
+ *                       head_dim % 8 != 0, self-attention n % 8 != 0;
+ *   TG_ERR_ARG          null pointers and pitch violations, as the narrow entry points.
+ * Additive to ABI 308: two new symbols, no struct change, TG_ABI_VERSION unchanged. */
+int tg_attention_bwd_wide(const tg_attn_bwd_desc* d, void* stream);
+int tg_attention_bwd_cross_wide(const tg_attn_bwd_cross_desc* d, void* stream);
 
 /* Attention-probability export (the save_attn_to_dict side channel, attention_processor.py:532-551):
  * probs[b - b0, h, i, t] = softmax_j(s q_i . k_j)[tokens[t]] for batch items b in [b0, batch), fp32 out

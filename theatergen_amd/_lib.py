@@ -138,6 +138,8 @@ SIGNATURES = {
     "tg_attention": (i32, [C.POINTER(AttnDesc), vp]),
     "tg_attention_bwd": (i32, [C.POINTER(AttnBwdDesc), vp]),
     "tg_attention_bwd_cross": (i32, [C.POINTER(AttnBwdCrossDesc), vp]),
+    "tg_attention_bwd_wide": (i32, [C.POINTER(AttnBwdDesc), vp]),
+    "tg_attention_bwd_cross_wide": (i32, [C.POINTER(AttnBwdCrossDesc), vp]),
     "tg_attn_probs": (i32, [i32, i32, i32, i32, i32, i32, vp, i64, i64, vp, i64, i64, i32, f32, vp, i32, vp, vp]),
     "tg_groupnorm_scratch_bytes": (i64, [i32, i64, i32]),
     "tg_groupnorm": (i32, [i32, vp, vp, i32, i32, i32, i64, i32, f32, vp, vp, i32, vp, vp, vp]),

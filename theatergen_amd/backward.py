@@ -28,6 +28,7 @@ from .weights_pack import pack_conv1x1, pack_conv3x3
 
 
 FLASH_BWD = os.environ.get("TG_FLASH_BWD", "1") != "0"     # dev A/B knob: 0 = the materialised per-(item, head) reverse pass for every layer
+FLASH_BWD_WIDE = os.environ.get("TG_FLASH_BWD_WIDE", "0") != "0"   # opt-in: 64 < head dim <= 160 (SD-1.5's inner levels) through tg_attention_bwd_wide / _cross_wide
 
 
 class _StopForward(Exception):
@@ -158,24 +159,28 @@ def attention_input_grad(attn, proc, h2d, B, N, enc, dout, extra):
         else:
             e2 = enc.contiguous().reshape(B * Ltot, ctx)
             segs.append((ops.linear(e2, attn.to_k.weight), ops.linear(e2, attn.to_v.weight), Ltot, 1.0, extra))
-    if self_attn and FLASH_BWD and ops.attention_bwd_supported(d, N):
-        # recompute-based reverse pass (round 5, tg_attention_bwd): no N x N matrix, three launches for all (item, head) pairs
+    wide = FLASH_BWD and FLASH_BWD_WIDE
+    if self_attn and (FLASH_BWD and ops.attention_bwd_supported(d, N) or wide and ops.attention_bwd_wide_supported(d, N)):
+        # recompute-based reverse pass (round 5, tg_attention_bwd; its wide twin for 64 < d <= 160): no N x N matrix, three launches for all (item, head) pairs
         k2d, v2d = segs[0][0], segs[0][1]
-        dq, dk, dv = ops.attention_bwd(q, k2d, v2d, do.contiguous(), B, N, heads, d, attn.scale)
+        bwd = ops.attention_bwd if d <= 64 else ops.attention_bwd_wide
+        dq, dk, dv = bwd(q, k2d, v2d, do.contiguous(), B, N, heads, d, attn.scale)
         dx = _dgrad_lin(dq, _lin_t(attn, "q", attn.to_q.weight))
         wk, wv = _lin_t(attn, "k", attn.to_k.weight), _lin_t(attn, "v", attn.to_v.weight)
         dx = ops.gemm(dk, wk, B * N, wk.shape[0], wk.shape[1], res=dx)
         dx = ops.gemm(dv, wv, B * N, wv.shape[0], wv.shape[1], res=dx)
         return dx
-    if not self_attn and FLASH_BWD and d % 8 == 0 and d <= 64:
-        # cross-attention: constant K / V, one softmax per segment (text, IP-Adapter image keys): statistics + dQ launches per segment (tg_attention_bwd_cross)
+    if not self_attn and d % 8 == 0 and (FLASH_BWD and d <= 64 or wide and 64 < d <= 160):
+        # cross-attention: constant K / V, one softmax per segment (text, IP-Adapter image keys): statistics + dQ launches per segment (tg_attention_bwd_cross
+        # / _cross_wide)
+        bwd_cross = ops.attention_bwd_cross if d <= 64 else ops.attention_bwd_cross_wide
         dq = None
         doc = do.contiguous()
         for k2d, v2d, L, wgt, ex in segs:
             if wgt == 0.0:
                 continue
-            part = ops.attention_bwd_cross(q, doc, k2d, v2d, B, N, L, heads, d, attn.scale, attn.scale * wgt,
-                                           extra=ex.contiguous() if ex is not None else None)
+            part = bwd_cross(q, doc, k2d, v2d, B, N, L, heads, d, attn.scale, attn.scale * wgt,
+                             extra=ex.contiguous() if ex is not None else None)
             dq = part if dq is None else dq + part
         if dq is None:
             dq = torch.zeros_like(q)

@@ -622,11 +622,16 @@ def attention_bwd_supported(head_dim, n):
 def attention_bwd(q, k, v, dout, batch, n, heads, head_dim, scale):
     """Self-attention reverse pass without materialised probabilities: q, k, v, dout [batch * n, heads * head_dim] (contiguous rows) ->
     (dq, dk, dv) in the same layout.  Three launches of one kernel (+ three tg_transpose launches for the streamed K^T / Q^T / dO^T tiles)."""
+    return _attention_bwd("tg_attention_bwd", q, k, v, dout, batch, n, heads, head_dim, scale)
+
+
+def _attention_bwd(entry, q, k, v, dout, batch, n, heads, head_dim, scale):
+    name = entry[3:]
     _need_cuda(q)
     inner = heads * head_dim
     for t in (q, k, v, dout):
         if t.shape != (batch * n, inner) or not t.is_contiguous() or t.dtype != q.dtype:
-            raise RuntimeError("attention_bwd: q, k, v, dout must be contiguous [batch * n, heads * head_dim] tensors of one dtype")
+            raise RuntimeError(name + ": q, k, v, dout must be contiguous [batch * n, heads * head_dim] tensors of one dtype")
     L = _lib.lib()
     qt, kt, dot = transpose(q, batch, n, inner), transpose(k, batch, n, inner), transpose(dout, batch, n, inner)
     stats = torch.empty((batch, heads, n, 2), dtype=torch.float32, device=q.device)
@@ -640,13 +645,17 @@ def attention_bwd(q, k, v, dout, batch, n, heads, head_dim, scale):
     d.stats = _ptr(stats)
     d.dq, d.dk, d.dv = _ptr(dq), _ptr(dk), _ptr(dv)
     d.scale = float(scale)
-    _lib.check(L.tg_attention_bwd(C.byref(d), _stream()))
+    _lib.check(getattr(L, entry)(C.byref(d), _stream()))
     return dq, dk, dv
 
 
 def attention_bwd_cross(q, dout, k, v, batch, n_q, n_k, heads, head_dim, scale, ds_scale, extra=None):
     """dQ of one softmax segment of cross-attention (constant K / V): q, dout [batch * n_q, inner], k, v [batch * n_k, inner];
     ``extra`` fp32 [batch, heads, n_q, n_k] = d loss / d P or None.  Two launches (row statistics, dQ) for all (item, head) pairs."""
+    return _attention_bwd_cross("tg_attention_bwd_cross", q, dout, k, v, batch, n_q, n_k, heads, head_dim, scale, ds_scale, extra)
+
+
+def _attention_bwd_cross(entry, q, dout, k, v, batch, n_q, n_k, heads, head_dim, scale, ds_scale, extra):
     _need_cuda(q)
     inner = heads * head_dim
     lp = (n_k + 7) // 8 * 8
@@ -661,12 +670,27 @@ def attention_bwd_cross(q, dout, k, v, batch, n_q, n_k, heads, head_dim, scale, 
     d.kt, d.t_ld, d.t_bs = _ptr(kt), lp, inner * lp
     if extra is not None:
         if extra.dtype != torch.float32 or extra.shape != (batch, heads, n_q, n_k) or not extra.is_contiguous():
-            raise RuntimeError("attention_bwd_cross: extra must be a contiguous fp32 [batch, heads, n_q, n_k] tensor")
+            raise RuntimeError(entry[3:] + ": extra must be a contiguous fp32 [batch, heads, n_q, n_k] tensor")
         d.extra, d.extra_ld = _ptr(extra), n_k
     d.stats, d.dq = _ptr(stats), _ptr(dq)
     d.scale, d.ds_scale = float(scale), float(ds_scale)
-    _lib.check(_lib.lib().tg_attention_bwd_cross(C.byref(d), _stream()))
+    _lib.check(getattr(_lib.lib(), entry)(C.byref(d), _stream()))
     return dq
+
+
+def attention_bwd_wide_supported(head_dim, n):
+    """True when tg_attention_bwd_wide (the recompute-based self-attention reverse pass for 64 < head_dim <= 160) takes the problem."""
+    return head_dim % 8 == 0 and 64 < head_dim <= 160 and n % 8 == 0
+
+
+def attention_bwd_wide(q, k, v, dout, batch, n, heads, head_dim, scale):
+    """``attention_bwd`` for 64 < head_dim <= 160 (tg_attention_bwd_wide): same arguments, transposes and ``stats`` scratch."""
+    return _attention_bwd("tg_attention_bwd_wide", q, k, v, dout, batch, n, heads, head_dim, scale)
+
+
+def attention_bwd_cross_wide(q, dout, k, v, batch, n_q, n_k, heads, head_dim, scale, ds_scale, extra=None):
+    """``attention_bwd_cross`` for 64 < head_dim <= 160 (tg_attention_bwd_cross_wide): same arguments, zero-padded K^T and ``stats`` scratch."""
+    return _attention_bwd_cross("tg_attention_bwd_cross_wide", q, dout, k, v, batch, n_q, n_k, heads, head_dim, scale, ds_scale, extra)
 
 
 def transpose(src, batch, rows, cols, out=None):

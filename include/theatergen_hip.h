@@ -634,7 +634,11 @@ int tg_skinny_gemm(const tg_skinny_desc* d, void* stream);
  * (what attn.to_out consumes).  `wq` / `ln_u` / `ln_v`: LayerNorm fold of (softmax scale * log2 e) * to_q (host: weights_pack.pack_ln_linear);
  * `kv`: the conditioning's K / V^T as MFMA fragments (tg_xq_kv_pack from the projections tg_gemm writes: k [B * L, C], vt [B, C, ldt], kip, vtip),
  * tg_xq_kv_bytes bytes; `ip_scale`: device scalar or NULL (= 1.0).  head_dim 80 | 160, C % 320 == 0, M and rows_per_batch multiples of 128, text_len <= 96,
- * ip_tokens <= 16. */
+ * ip_tokens <= 16.
+ * head_dim 64 (SD-2.1 / SDXL): the same launch on 128 x 128 tiles, two heads of 64 per tile — C % 128 == 0, the other conditions as above.  Any other head dim, and
+ * head_dim 64 with C % 128 != 0, is TG_ERR_UNSUPPORTED (the caller keeps its three-launch path); every other violated condition is TG_ERR_ARG.
+ * tg_xq_kv_bytes: batch * (C / tile width) * pieces per tile KiB — 60 (head_dim 64, tile width 128), 82 (80, 160) or 75 (160, 160) fragments of 1 KiB; -1 for a
+ * geometry tg_xq_attn does not take.  tg_xq_kv_pack: per tile and head K by key block x k-step, then V^T by row block x key k-step; the tile stride in channels is the tile width. */
 typedef struct {
   int32_t dtype;
   const void* x; int64_t ldx;

@@ -191,16 +191,26 @@ def ln_weight(attn, name, norm):
 # TG_XQ=0 switches it off (old three-launch path); TG_XQ_MIN_ROWS: below this many token rows the 128 x 160 tiling leaves most of the chip idle
 XQ_ENABLED = os.environ.get("TG_XQ", "1") != "0"
 XQ_MIN_ROWS = int(os.environ.get("TG_XQ_MIN_ROWS", "4096"))
+# head dim 64 (SD-2.1 / SDXL: 128 x 128 tiles, two heads per tile): opt-in with TG_XQ_D64=1; TG_XQ_D64_MIN_ROWS: the smallest token-row count at which the
+# fused launch measured no slower than the three-launch path (profiles/xq_d64_findings.md)
+XQ_D64_ENABLED = os.environ.get("TG_XQ_D64", "0") == "1"
+XQ_D64_MIN_ROWS = int(os.environ.get("TG_XQ_D64_MIN_ROWS", "256"))
 
 
 def xq_eligible(attn, x2d, B, N, L, T, kwargs):
-    """inner-level geometry the fused launch is built for: square to_q with C % 320 == 0, head dim 80 | 160, whole 128-token tiles per batch item,
-    <= 96 text and <= 16 image keys; nothing that needs q or the probabilities afterwards (capture, masks)"""
+    """inner-level geometry the fused launch is built for: square to_q with C % 320 == 0 and head dim 80 | 160 — or, with ``XQ_D64_ENABLED``, C % 128 == 0
+    and head dim 64 —, whole 128-token tiles per batch item, <= 96 text and <= 16 image keys; nothing that needs q or the probabilities afterwards
+    (capture, masks)"""
     if not XQ_ENABLED or x2d.dtype not in (torch.bfloat16, torch.float16):
         return False
     inner, heads, d = attn_dims(attn)
     C = x2d.shape[1]
-    if inner != C or attn.to_q.weight.shape[1] != C or C % 320 or d not in (80, 160) or N % 128 or B * N < XQ_MIN_ROWS:
+    if inner != C or attn.to_q.weight.shape[1] != C or N % 128:
+        return False
+    if d == 64:
+        if not XQ_D64_ENABLED or C % 128 or B * N < XQ_D64_MIN_ROWS:
+            return False
+    elif C % 320 or d not in (80, 160) or B * N < XQ_MIN_ROWS:
         return False
     if L < 1 or L > 96 or T < 0 or T > 16 or x2d.stride(0) != C or x2d.stride(1) != 1:
         return False

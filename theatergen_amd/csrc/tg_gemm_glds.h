@@ -46,12 +46,13 @@ template <> __device__ __forceinline__ void ln_row_sums<f16_t>(f16x8 x, float& s
   }
 }
 
-// XA = 80 | 160 (tg_xattn_epi.h; LN = 1, 128 x 160 tiles only): the tile is the LayerNorm-folded to_q of two heads of 80 / one head of 160 channels and the
-// kernel's output is the cross-attention result O of those heads — W rows are read with bits 2 / 3 of the MFMA row swapped (q comes out as B fragments).
+// XA = 80 | 160 (tg_xattn_epi.h; LN = 1, 128 x 160 tiles only) and XA = 64 (128 x 128 tiles only): the tile is the LayerNorm-folded to_q of two heads of
+// 80 / one head of 160 / two heads of 64 channels and the kernel's output is the cross-attention result O of those heads — W rows are read with bits 2 / 3 of the MFMA row swapped (q comes out as B fragments).
 template <typename T, int BM, int BN, int WAVES_M, int WAVES_N, bool CONV, int STAGES, int BKT, int EPI, int LN = 0, int XA = 0>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) __attribute__((amdgpu_waves_per_eu((LN != 0 && STAGES == 3 && BKT == 32) ? 3 : 2)))
 void gemm_glds_kernel(GemmParams p) {
-  static_assert(XA == 0 || (LN == 1 && BM == 128 && BN == 160 && WAVES_M == 4 && WAVES_N == 1 && BKT == 64 && !CONV && EPI == 0), "XA: the 128 x 160 LayerNorm-folded tile");
+  static_assert(XA == 0 || (LN == 1 && BM == 128 && ((BN == 160 && (XA == 80 || XA == 160)) || (BN == 128 && XA == 64)) && WAVES_M == 4 && WAVES_N == 1 && BKT == 64 &&
+                            !CONV && EPI == 0), "XA: the 128 x 160 (head dim 80 / 160) or 128 x 128 (head dim 64) LayerNorm-folded tile");
   constexpr int NW = WAVES_M * WAVES_N;
   constexpr int PF = STAGES - 1;              // K-tiles kept in flight ahead of the one being multiplied
   constexpr int CH = BKT / 8;                 // 16-byte chunks per LDS row (8 at BK = 64, 4 at BK = 32)
@@ -425,7 +426,7 @@ void gemm_glds_kernel(GemmParams p) {
     }
     if constexpr (XA != 0) {
       // cross-attention of the tile's heads on the q the accumulators hold; O^T comes back in `acc` (standard layout) and leaves as a plain tile
-      xattn_epilogue<T, XA>(p, acc, smem, wave, lane, m0, n0, tile_n);
+      xattn_epilogue<T, XA, TN>(p, acc, smem, wave, lane, m0, n0, tile_n);
       GemmParams po = p;
       po.bias = nullptr; po.bvec = nullptr; po.res = nullptr; po.n_split = 0; po.out_scale = 1.0f; po.act = TG_ACT_NONE; po.geglu = 0;
       epilogue_tile_lds<T, TM, TN, EPI, false>(po, acc, m0 + wave_m * TM * 32, n0 + wave_n * TN * 32, lane,

@@ -14,6 +14,8 @@
 //     rounded for the PV product — what the reference's half-precision softmax output does;
 //   * O^T accumulates in the standard accumulator layout (V^T rows unswapped), two heads of 80 into one 160-channel tile (the shared 32-row block takes
 //     zero rows from the other head), and leaves through the GEMM's LDS-transposed epilogue: q and the attention launch never exist.
+// XA = 64 (SD-2.1 / SDXL: every head is 64 wide): the same epilogue on the 128 x 128 tile — two heads fill the tile exactly (head h owns O^T blocks 2h and
+// 2h + 1, no shared block), q is 8 fragments, and both heads' fragments (2 x 30 KiB) fit the two dead operand stages, so they come in ONE DMA batch.
 #pragma once
 #include "tg_gemm_common.h"
 
@@ -23,11 +25,14 @@ __device__ __forceinline__ int xa_swap23(int i) { return (i & ~12) | ((i & 4) <<
 
 // pieces (1 KiB fragments) of one head's K / V^T set: K: 4 key blocks (3 text, 1 image) x D / 16 k-steps; V^T: DBH row blocks x 7 key k-steps (6 text, 1 image)
 template <int D> struct XaGeom {
+  static constexpr int TW = D == 64 ? 128 : 160;    // tile width in channels: 64 -> 128 x 128 tiles, 80 / 160 -> 128 x 160
   static constexpr int KS = D / 16;                 // q / K k-steps per head
-  static constexpr int DBH = D == 80 ? 3 : 5;       // 32-row blocks of O^T a head touches
-  static constexpr int HPT = 160 / D;               // heads per 160-column tile
-  static constexpr int NPH = 4 * KS + 7 * DBH;      // pieces per head: 41 / 75
-  static constexpr int NPT = HPT * NPH;             // pieces per tile: 82 / 75
+  static constexpr int DBH = D == 80 ? 3 : D / 32;  // 32-row blocks of O^T a head touches: 2 / 3 / 5
+  static constexpr int HPT = TW / D;                // heads per tile
+  static constexpr int NPH = 4 * KS + 7 * DBH;      // pieces per head: 30 / 41 / 75
+  static constexpr int NPT = HPT * NPH;             // pieces per tile: 60 / 82 / 75
+  static constexpr bool ONE_BATCH = D == 64;        // both heads' fragments in one DMA batch (60 KiB <= two operand stages of the 128 x 128 tile)
+  static constexpr int NPB = ONE_BATCH ? NPT : NPH; // pieces per DMA batch
 };
 
 __device__ __forceinline__ float xa_other_half(float v) {
@@ -35,15 +40,16 @@ __device__ __forceinline__ float xa_other_half(float v) {
   return __shfl_xor(v, 32, 64);
 }
 
-template <typename T, int D>
-__device__ __forceinline__ void xattn_epilogue(const GemmParams& p, f32x16 (&acc)[1][5], char* smem, int wave, int lane, long m0, long n0, int tile_n) {
+template <typename T, int D, int TN>
+__device__ __forceinline__ void xattn_epilogue(const GemmParams& p, f32x16 (&acc)[1][TN], char* smem, int wave, int lane, long m0, long n0, int tile_n) {
   typedef typename Vec<T>::v8 V8;
   typedef XaGeom<D> G;
+  static_assert(TN * 32 == G::TW, "xattn_epilogue: wave tile width = the head dim's tile width");
   const int l31 = lane & 31, hi = lane >> 5;
-  // ---- q = acc + v (the LayerNorm fold's fp32 vector, permuted like the W rows), rounded: B fragments of the 10 k-steps of the tile
-  V8 qb[10];
+  // ---- q = acc + v (the LayerNorm fold's fp32 vector, permuted like the W rows), rounded: B fragments of the 2 TN (10 / 8) k-steps of the tile
+  V8 qb[2 * TN];
 #pragma unroll
-  for (int j = 0; j < 5; ++j)
+  for (int j = 0; j < TN; ++j)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const f32x4 v4 = *reinterpret_cast<const f32x4*>(p.ln_v + n0 + 32 * j + 16 * (g >> 1) + 8 * hi + 4 * (g & 1));
@@ -51,7 +57,7 @@ __device__ __forceinline__ void xattn_epilogue(const GemmParams& p, f32x16 (&acc
       for (int e = 0; e < 4; ++e) qb[2 * j + (g >> 1)][4 * (g & 1) + e] = from_f32<T>(acc[0][j][4 * g + e] + v4[e]);
     }
 #pragma unroll
-  for (int j = 0; j < 5; ++j)
+  for (int j = 0; j < TN; ++j)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[0][j][r] = 0.f;
   const long bi = m0 / p.xa_rows_per_batch;                      // the tile's batch item (uniform: rows_per_batch % 128 == 0)
@@ -60,13 +66,15 @@ __device__ __forceinline__ void xattn_epilogue(const GemmParams& p, f32x16 (&acc
   const int L = p.xa_L, Tn = p.xa_T;
 #pragma unroll
   for (int h = 0; h < G::HPT; ++h) {
-    __syncthreads();                                            // LDS free: K loop / LayerNorm vectors / the previous head's fragments are done with
-    for (int q = wave; q < G::NPH; q += 4)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(blob + (long)(h * G::NPH + q) * 1024 + lane * 16),
-                                       (__attribute__((address_space(3))) void*)(smem + q * 1024), 16, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const char* kf = smem + lane * 16;
+    if (!G::ONE_BATCH || h == 0) {
+      __syncthreads();                                          // LDS free: K loop / LayerNorm vectors / the previous head's fragments are done with
+      for (int q = wave; q < G::NPB; q += 4)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(blob + (long)(h * G::NPH + q) * 1024 + lane * 16),
+                                         (__attribute__((address_space(3))) void*)(smem + q * 1024), 16, 0, 0);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+    const char* kf = smem + (G::ONE_BATCH ? h * G::NPH * 1024 : 0) + lane * 16;
     // ---- S^T[key block][query] = K q^T over the head's k-steps
     f32x16 s[4];
 #pragma unroll
@@ -115,7 +123,7 @@ __device__ __forceinline__ void xattn_epilogue(const GemmParams& p, f32x16 (&acc
       for (int e = 0; e < 8; ++e) pb[e] = from_f32<T>(s[kb][8 * sp + e] * wgt);
 #pragma unroll
       for (int db = 0; db < G::DBH; ++db) {
-        const int gb = D == 80 ? 2 * h + db : db;               // global 32-row block of the tile's O^T
+        const int gb = G::HPT == 2 ? 2 * h + db : db;           // global 32-row block of the tile's O^T
         acc[0][gb] = mfma32(*reinterpret_cast<const V8*>(vf + (db * 7 + ks) * 1024), pb, acc[0][gb]);
       }
     }

@@ -276,10 +276,12 @@ def xq_attn(x, wq, ln_u, ln_v, ln_eps, kv, head_dim, rows_per_batch, text_len, i
     d.kv, d.ip_scale = _ptr(kv), _ptr(ip_scale)
     d.out, d.ldc = _ptr(out), int(out.stride(0))
     d.M, d.C, d.head_dim, d.rows_per_batch, d.text_len, d.ip_tokens = int(M), int(Cc), int(head_dim), int(rows_per_batch), int(text_len), int(ip_tokens)
-    heads = Cc // head_dim
     L_ = text_len + ip_tokens
+    # algorithmic count: to_q + QK^T + PV on the live keys.  It does not depend on the tile (head dim 64: 128 x 128 tiles whose two heads fill every O^T
+    # block; 80: 128 x 160 with a shared block) — the padded key slots and zero rows a tile multiplies are not counted as work
     flops = 2.0 * M * Cc * Cc + 4.0 * M * L_ * Cc
-    _profiled(lambda: _lib.check(_lib.lib().tg_xq_attn(C.byref(d), _stream())), f"gemm_glds_kernel<plain+ln+xattn d{head_dim},128x160>", M, Cc, Cc, flops,
+    tile = "128x128" if int(head_dim) == 64 else "128x160"
+    _profiled(lambda: _lib.check(_lib.lib().tg_xq_attn(C.byref(d), _stream())), f"gemm_glds_kernel<plain+ln+xattn d{head_dim},{tile}>", M, Cc, Cc, flops,
               alg_bytes=2.0 * (2 * M * Cc + Cc * Cc) + 2.0 * (M // rows_per_batch) * 2 * L_ * Cc)
     return out
 

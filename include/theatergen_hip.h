@@ -253,7 +253,7 @@ typedef struct {
   float scale, ds_scale;
 } tg_attn_bwd_cross_desc;
 int tg_attention_bwd_cross(const tg_attn_bwd_cross_desc* d, void* stream);
-/* The two reverse passes above for WIDE heads, 64 < head_dim <= 160, head_dim % 8 == 0 (SD-1.5's inner levels: d = 80 / 160; csrc/tg_attention_bwd_wide.hip).
+/* The two reverse passes above for WIDE heads, 64 < head_dim <= 160, head_dim % 8 == 0 (SD-1.5's inner levels: d = 80 / 160; csrc/tg_attention_bwd.hip, the same kernel template).
  * Same descriptors, same contract text, same roundings and launch structure (statistics, dQ, and for self-attention dK + dV); tg_attention_bwd_cross_wide keeps
  * the zero-padded `kt` rule and the `extra` rule.  For head_dim > 96 the output columns of a launch are split over two workgroups, each of which
  * recomputes the scores over the full head dim; every output element is still written by exactly one lane, no atomics.

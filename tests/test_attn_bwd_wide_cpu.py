@@ -1,5 +1,5 @@
 """CPU: the wide-head reverse pass of attention (``tg_attention_bwd_wide`` / ``tg_attention_bwd_cross_wide``, 64 < head_dim <= 160;
-csrc/tg_attention_bwd_wide.hip) — what can be pinned without a device.
+csrc/tg_attention_bwd.hip) — what can be pinned without a device.
 
   * the header declares both symbols, ``_lib.SIGNATURES`` binds them, the library exports them, and the ABI version did not move (the change is
     additive);

@@ -1,4 +1,4 @@
-"""GPU: ``tg_attention_bwd_wide`` / ``tg_attention_bwd_cross_wide`` (csrc/tg_attention_bwd_wide.hip: the recompute reverse pass of attention for
+"""GPU: ``tg_attention_bwd_wide`` / ``tg_attention_bwd_cross_wide`` (csrc/tg_attention_bwd.hip: the recompute reverse pass of attention for
 64 < head_dim <= 160 — SD-1.5's inner levels) against the fp64 restatement of the C-ABI contract (tests/attn_bwd_contract.py), the ``ops``
 wrappers, and the opt-in routing of ``backward.attention_input_grad`` (``backward.FLASH_BWD_WIDE``).
 

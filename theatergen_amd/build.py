@@ -140,11 +140,12 @@ HOT_GATES = [
     ("rc_front_kernel<", 0, 216),                                  # round 4's first version spilled 108 registers (30 % of its launch)
     ("rc_linear_kernel<", 0, 256),                                 # every instance (the UNet launches <T,20,8,2,false,0>, plain / + residual)
     ("skinny_gemm_kernel<", 0, 256),                               # round 5: the CK = 16 / 20 instances spilled 44 .. 164 bytes
-    ("attn_bwd_kernel<", 0, 224),                                  # round 5: reverse pass of attention (statistics / dQ / dK + dV instances: 156 / 198 / 216 VGPRs)
-    # reverse pass of attention for 64 < d <= 160, one wave per SIMD (unified 512-register file; VGPRs + AGPRs): statistics / dQ / dK + dV instances
-    # <.,6,3> 168+64 / 228+64 / 204+96, <.,8,2> 188+64 / 226+64 / 215+64, <.,10,3> 204+64 / 256+68 / 235+96.  Scratch 0 is the condition: spilled
-    # accumulators are what this shape risks
-    ("attn_bwd_wide_kernel<", 0, 256),
+    # reverse pass of attention, one kernel template <NKS, OT, T, MODE> (tg_attention_bwd.hip).  <4,2,..> is d <= 64 at two waves per SIMD
+    # (round 5; statistics / dQ / dK + dV instances: 156 / 198 / 216 VGPRs).  The rest is 64 < d <= 160 at one wave per SIMD (unified 512-register
+    # file; VGPRs + AGPRs): <6,3,..> 168+64 / 228+64 / 204+96, <8,2,..> 188+64 / 226+64 / 215+64, <10,3,..> 204+64 / 256+68 / 235+96.  Scratch 0 is
+    # the condition: spilled accumulators are what this shape risks
+    ("attn_bwd_kernel<4,2,", 0, 224),
+    ("attn_bwd_kernel<", 0, 256),
     # round 6: ping-pong 256 x 256 GEMM.  Template arguments <T, EPI, LN>: nothing spilled in the GEGLU / linear / activation instances; the
     # LayerNorm-folded linear instance (q | k | v^T) spills in its EPILOGUE only (scripts/asm_loop_report.py: 0 scratch accesses inside the MFMA loop)
     ("pp_gemm_kernel<bf16,2,", 0, 256),

@@ -1,4 +1,5 @@
-// Recompute-based (flash-style) reverse pass of self-attention, head dim <= 64 (round 5; tg_attention_bwd).
+// Recompute-based (flash-style) reverse pass of attention, head dims 8 .. 160 (round 5; tg_attention_bwd / tg_attention_bwd_cross for d <= 64,
+// tg_attention_bwd_wide / tg_attention_bwd_cross_wide for 64 < d <= 160: SD-1.5's inner levels, d = 80 at 32 x 32, d = 160 at 16 x 16 / 8 x 8 and the mid block).
 //
 // The guidance reverse pass (models/pipelines.py:62-128: `torch.autograd.grad(loss, latents)` through the whole UNet) needs, per self-attention layer,
 //     dQ = dS K,  dK = dS^T Q,  dV = P^T dO,      P = softmax(s Q K^T),  dS = s P o (dO V^T - D),  D[q] = sum_k P[q, k] (dO V^T)[q, k]
@@ -13,7 +14,18 @@
 // Data path = the forward kernel's (tg_attention.hip): 64-row tiles as 128-byte LDS rows filled by LDS-DMA with the XOR swizzle, two stages, one
 // barrier per tile; score tiles with the streamed rows on the ACCUMULATOR rows in the bit-2/3-swapped order, so that 8 consecutive registers are 8
 // consecutive streamed rows = the B fragment of the following product as they stand (P and dS are rounded to the storage dtype there — what the
-// materialised path stored).  Deterministic: no atomics, every output element is written by one lane.
+// materialised path stored; D comes from the unrounded P).  Deterministic: no atomics, every output element is written by one lane.
+//
+// What the head dim changes (template arguments <NKS, OT> of attn_bwd_kernel; mathematics, roundings and data path are the same for all):
+//   - the score contraction takes NKS = 4 / 6 / 8 / 10 k-steps of 16 (d <= 64 / 96 / 128 / 160); a streamed tile is ceil(NKS / 4) column panels of
+//     64 x 64; the two register-side fragments are 2 x NKS x 4 registers (80 at d = 160);
+//   - the output (dQ^T, or dK^T and dV^T) is OT <= 3 tiles of 32 columns per workgroup (d <= 64: 2, d <= 96: 3).  For d > 96 the OUTPUT COLUMNS are
+//     split over two workgroups (grid factor 2: d <= 128 -> 2 + 2 tiles, d <= 160 -> 3 + 2 tiles): each contracts the scores over the full d (they
+//     are recomputed twice — those layers have N <= 256 in SD-1.5 and are launch-bound) and stages only its own OT x 32 rows of the transposed tiles;
+//   - d <= 64 runs at least two waves per SIMD (at most 224 registers, 65 KB of LDS for the two stages).  d > 64 runs one wave per SIMD (four
+//     waves = one workgroup per CU): the unified 512-register file holds fragments (80) + two score tiles (64) + accumulators (96 in the dK + dV
+//     mode) without scratch, and the two stages may take up to 146 KB of the CU's 160 KB of LDS
+//     (stage = 2 x ceil(NKS / 4) x 8 KB of row panels + 2 x OT x 4 KB of transposed half-panels + 1 KB of statistics).
 #include "tg_common.h"
 
 namespace {
@@ -25,6 +37,8 @@ struct AttnBwdParams {
   int n_z;                                               // columns of the transposed streamed tensors that may be read (n_s rounded up to 8: zero padding)
   const float* extra; long e_ld;                         // MODE 0 / 2, optional: d loss / d P added to dP, fp32 [batch][heads][n_r][e_ld >= n_s] (cross-attention guidance term)
   float ds_scale;                                        // dS = ds_scale * P o (dP - D)   (softmax scale x the segment's output weight)
+  int n_split;                                           // NKS > 4 only: workgroups per (row block, head, item), each owns output columns [half * OT * 32, +OT * 32).
+                                                         // In what was padding: the NKS == 4 kernels' argument offsets, and with them their code, stay as they were
   const void* r1; const void* r2; long r_ld, r_bs;       // register-side rows [n_r][...]: MODE 0 / 2: Q, dO;  MODE 1: K, V
   const void* s1; const void* s2; long s_ld, s_bs;       // streamed rows [n_s][...]:      MODE 0 / 2: K, V;   MODE 1: Q, dO
   const void* z1; const void* z2; long z_ld, z_bs;       // streamed tensors transposed [inner][n_s]: MODE 0: K^T;  MODE 1: Q^T, dO^T
@@ -33,11 +47,22 @@ struct AttnBwdParams {
   float scale, scale_log2;
 };
 
-template <typename T, int MODE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void attn_bwd_kernel(AttnBwdParams p) {
+template <int NKS, int OT>
+struct AttnBwdLds {
+  static constexpr int NP = (NKS + 3) / 4, PANEL = 64 * 64, HPANEL = 32 * 64;
+  static constexpr int ZOFF = 2 * NP * PANEL, STOFF = ZOFF + 2 * OT * HPANEL, STAGE = STOFF + 512;     // elements
+};
+
+// ONE kernel for every head dim.  NKS == 4 (d <= 64) runs two waves per SIMD and never splits its output columns: no split arithmetic exists in those
+// instances and p.n_split is not read.  NKS > 4 runs one wave per SIMD, p.n_split (1 or 2) workgroups per problem.
+template <int NKS, int OT, typename T, int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NKS > 4 ? 1 : 2, NKS > 4 ? 1 : 0)))      // (2): at least two;  (1, 1): exactly one
+void attn_bwd_kernel(AttnBwdParams p) {
+  constexpr bool SPLIT = NKS > 4;
   typedef typename Vec<T>::v8 V8;
   typedef typename Vec<T>::v4 V4;
-  constexpr int NKS = 4, DT = 2, KV = 64, PANEL = 64 * 64, STAGE = 4 * PANEL + 512;
+  typedef AttnBwdLds<NKS, OT> G;
+  constexpr int KV = 64, NP = G::NP, PANEL = G::PANEL, HPANEL = G::HPANEL, STAGE = G::STAGE;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* sbase = reinterpret_cast<T*>(smem);
 
@@ -48,13 +73,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, xcd = blockIdx.x & 7;
     lbid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
   }
+  int dbase = 0;                                           // first output column (= row of the transposed tiles) of this workgroup
+  if constexpr (SPLIT) {
+    dbase = lbid % p.n_split * (OT * 32);                  // the two halves of one problem are neighbours of the walk: they share every input tile
+    lbid /= p.n_split;
+  }
   const int rblk = lbid % p.n_rblk;
   const int h = (lbid / p.n_rblk) % p.heads, b = lbid / (p.n_rblk * p.heads);
   const int HD = p.hd;
   const long rrow = (long)rblk * 128 + wave * 32 + l31;
   const bool r_ok = rrow < p.n_r;
 
-  // register-side fragments (B operands): this lane's row, d = ks*16 + hi*8 .. +8
+  // register-side fragments (B operands): this lane's row, d = ks*16 + hi*8 .. +8, over the FULL head dim
   V8 r1f[NKS], r2f[NKS];
   {
     const T* p1 = reinterpret_cast<const T*>(p.r1) + (long)b * p.r_bs + rrow * p.r_ld + (long)h * HD;
@@ -73,14 +103,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
   float lse_l = 0.f, d_l = 0.f;
   if (MODE == 0 && r_ok) { lse_l = statb[2 * rrow]; d_l = statb[2 * rrow + 1]; }
 
-  f32x16 o1[DT], o2[DT];
+  f32x16 o1[OT], o2[OT];
 #pragma unroll
-  for (int t = 0; t < DT; ++t)
+  for (int t = 0; t < OT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) { o1[t][r] = 0.f; o2[t][r] = 0.f; }
   float m_run = -INFINITY, l_run = 0.f, num = 0.f;         // MODE 2 (per lane half: its 32 of every tile's 64 keys)
 
-  // ---- LDS-DMA tile loader (forward kernel's scheme: instruction q covers rows [8q, 8q + 8), lane -> (row 8q + lane / 8, 16-byte slot lane % 8))
+  // ---- LDS-DMA tile loader (forward kernel's scheme per 64-column panel: instruction q covers rows [8q, 8q + 8), lane -> (row 8q + lane / 8, 16-byte slot lane % 8))
   const int lrow = lane >> 3, slot = lane & 7;
   const T* zero = reinterpret_cast<const T*>(attn_bwd_zero_page);
   auto dma = [&](const T* src, T* lds_row_base) {
@@ -94,30 +124,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
   auto issue = [&](int s0, int stage) {
     T* st = sbase + stage * STAGE;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int q = j * 4 + wave;
-      const int row = 8 * q + lrow;
-      const int d0 = (slot ^ ((row >> 1) & 7)) << 3;
-      const bool ok = d0 < HD && s0 + row < p.n_s;
-      dma(ok ? s1b + (long)(s0 + row) * p.s_ld + d0 : zero, st + q * 512);
-      dma(ok ? s2b + (long)(s0 + row) * p.s_ld + d0 : zero, st + PANEL + q * 512);
-    }
-    if constexpr (MODE != 2) {
+    for (int pn = 0; pn < NP; ++pn)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int q = j * 4 + wave;
-        const int d = 8 * q + lrow;
-        const int c0 = s0 + ((slot ^ ((d >> 1) & 7)) << 3);
+        const int row = 8 * q + lrow;
+        const int d0 = pn * 64 + ((slot ^ ((row >> 1) & 7)) << 3);
+        const bool ok = d0 < HD && s0 + row < p.n_s;        // HD % 8 == 0: a 16-byte chunk is wholly inside or wholly outside the head
+        dma(ok ? s1b + (long)(s0 + row) * p.s_ld + d0 : zero, st + pn * PANEL + q * 512);
+        dma(ok ? s2b + (long)(s0 + row) * p.s_ld + d0 : zero, st + (NP + pn) * PANEL + q * 512);
+      }
+    if constexpr (MODE != 2) {
+      // this workgroup's OT x 32 rows of the transposed tiles: 4 x OT instructions of 8 rows, OT per wave
+#pragma unroll
+      for (int j = 0; j < OT; ++j) {
+        const int q = j * 4 + wave;
+        const int dl = 8 * q + lrow;
+        const int d = dbase + dl;
+        const int c0 = s0 + ((slot ^ ((dl >> 1) & 7)) << 3);
         const bool ok = d < HD && c0 < p.n_z;                // n_z % 8 == 0: a 16-byte chunk is wholly inside or wholly outside (columns >= n_s: zero padding)
-        dma(ok ? z1b + (long)d * p.z_ld + c0 : zero, st + 2 * PANEL + q * 512);
-        if constexpr (MODE == 1) dma(ok ? z2b + (long)d * p.z_ld + c0 : zero, st + 3 * PANEL + q * 512);
+        dma(ok ? z1b + (long)d * p.z_ld + c0 : zero, st + G::ZOFF + q * 512);
+        if constexpr (MODE == 1) dma(ok ? z2b + (long)d * p.z_ld + c0 : zero, st + G::ZOFF + OT * HPANEL + q * 512);
       }
     }
     if constexpr (MODE == 1) {
       if (wave == 0) {                                       // the tile's 64 (lse2, D) pairs: 512 bytes = lanes 0 .. 31
         const int idx = s0 + 2 * lane;
         const bool ok = lane < 32 && idx < p.n_s;
-        dma(ok ? reinterpret_cast<const T*>(statb + 2 * idx) : zero, st + 4 * PANEL);
+        dma(ok ? reinterpret_cast<const T*>(statb + 2 * idx) : zero, st + G::STOFF);
       }
     }
   };
@@ -139,7 +173,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     __builtin_amdgcn_s_barrier();
     if (t + 1 < nt) issue(s0 + KV, stg ^ 1);
     const T* sP1 = sbase + stg * STAGE;
-    const T* sP2 = sP1 + PANEL;
+    const T* sP2 = sP1 + NP * PANEL;
     // the two score-shaped products: rows = streamed items (permuted), columns = this lane's register-side row
     f32x16 s1[2], s2[2];
 #pragma unroll
@@ -148,8 +182,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
       for (int r = 0; r < 16; ++r) { s1[kvt][r] = 0.f; s2[kvt][r] = 0.f; }
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) {
-        const V8 f1 = *reinterpret_cast<const V8*>(sP1 + kofs[ks] + kvt * 32 * 64);
-        const V8 f2 = *reinterpret_cast<const V8*>(sP2 + kofs[ks] + kvt * 32 * 64);
+        const int o = (ks >> 2) * PANEL + kvt * 32 * 64;
+        const V8 f1 = *reinterpret_cast<const V8*>(sP1 + kofs[ks & 3] + o);
+        const V8 f2 = *reinterpret_cast<const V8*>(sP2 + kofs[ks & 3] + o);
         s1[kvt] = mfma32(f1, r1f[ks], s1[kvt]);
         s2[kvt] = mfma32(f2, r2f[ks], s2[kvt]);
       }
@@ -196,9 +231,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
       num = __builtin_fmaf(num, alpha, ns);
       m_run = m_new;
     } else {
-      const float* sst = reinterpret_cast<const float*>(sP1 + 4 * PANEL);
-      const T* sZ1 = sP1 + 2 * PANEL;
-      const T* sZ2 = sP1 + 3 * PANEL;
+      const float* sst = reinterpret_cast<const float*>(sP1 + G::STOFF);
+      const T* sZ1 = sP1 + G::ZOFF;
+      const T* sZ2 = sZ1 + OT * HPANEL;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int kvt = c >> 1, cc = c & 1;
@@ -224,11 +259,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
           dsf[j] = from_f32<T>(pe * (s2[kvt][r] - d8[j]) * p.ds_scale);
         }
 #pragma unroll
-        for (int t2 = 0; t2 < DT; ++t2) {
-          const V8 zf = *reinterpret_cast<const V8*>(sZ1 + vofs[c] + t2 * 32 * 64);
+        for (int t2 = 0; t2 < OT; ++t2) {
+          const V8 zf = *reinterpret_cast<const V8*>(sZ1 + vofs[c] + t2 * HPANEL);
           o1[t2] = mfma32(zf, dsf, o1[t2]);
           if constexpr (MODE == 1) {
-            const V8 zg = *reinterpret_cast<const V8*>(sZ2 + vofs[c] + t2 * 32 * 64);
+            const V8 zg = *reinterpret_cast<const V8*>(sZ2 + vofs[c] + t2 * HPANEL);
             o2[t2] = mfma32(zg, pf, o2[t2]);
           }
         }
@@ -249,15 +284,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     }
     return;
   }
-  // ---- store: accumulator rows d -> out[b, row, h*HD + d], 4 consecutive d per 8-byte store (forward kernel's store)
+  // ---- store: accumulator rows d -> out[b, row, h*HD + d], 4 consecutive d per 8-byte store (forward kernel's store); the workgroup's own columns only
   if (r_ok) {
     T* op1 = reinterpret_cast<T*>(p.out1) + (long)b * p.o_bs + rrow * p.o_ld + (long)h * HD;
     T* op2 = MODE == 1 ? reinterpret_cast<T*>(p.out2) + (long)b * p.o_bs + rrow * p.o_ld + (long)h * HD : nullptr;
 #pragma unroll
-    for (int t = 0; t < DT; ++t)
+    for (int t = 0; t < OT; ++t)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * hi;
+        const int d = dbase + t * 32 + 8 * g + 4 * hi;
         if (d < HD) {
           V4 v;
 #pragma unroll
@@ -274,17 +309,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
   }
 }
 
-template <typename T, int MODE>
-void launch_bwd(const AttnBwdParams& p, int batch, hipStream_t st) {
-  constexpr size_t lds = (size_t)2 * (4 * 64 * 64 + 512) * sizeof(T);
-  auto k = attn_bwd_kernel<T, MODE>;
+template <typename T, int MODE, int NKS, int OT>
+void launch(AttnBwdParams p, int batch, int n_split, hipStream_t st) {
+  constexpr size_t lds = (size_t)2 * AttnBwdLds<NKS, OT>::STAGE * sizeof(T);
+  static_assert(lds <= 160 * 1024, "two stages must fit the CU's LDS");
+  auto k = attn_bwd_kernel<NKS, OT, T, MODE>;
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   (void)attr;
-  hipLaunchKernelGGL(k, dim3((unsigned)(p.n_rblk * p.heads * batch)), dim3(256), lds, st, p);
+  p.n_split = MODE == 2 ? 1 : n_split;                     // the statistics have no output columns to split
+  hipLaunchKernelGGL(k, dim3((unsigned)(p.n_rblk * p.heads * batch * p.n_split)), dim3(256), lds, st, p);
+}
+
+// d <= 64: 4 k-steps, 2 output tiles;  d <= 96: 6 k-steps, 3 tiles;  d <= 128: 8 k-steps, 2 + 2 tiles;  d <= 160: 10 k-steps, 3 + 2 tiles
+template <typename T, int MODE>
+void launch_hd(const AttnBwdParams& p, int batch, hipStream_t st) {
+  if (p.hd <= 64) launch<T, MODE, 4, 2>(p, batch, 1, st);
+  else if (p.hd <= 96) launch<T, MODE, 6, 3>(p, batch, 1, st);
+  else if (p.hd <= 128) launch<T, MODE, 8, 2>(p, batch, 2, st);
+  else launch<T, MODE, 10, 3>(p, batch, 2, st);
 }
 
 template <typename T>
-int run_bwd(const tg_attn_bwd_desc* d, hipStream_t st) {
+int run_self(const tg_attn_bwd_desc* d, hipStream_t st) {
   AttnBwdParams p{};
   p.heads = d->heads; p.hd = d->head_dim; p.n_r = d->n; p.n_s = d->n; p.n_z = d->n; p.n_rblk = (d->n + 127) / 128;
   p.extra = nullptr; p.e_ld = 0; p.ds_scale = d->scale;
@@ -295,21 +341,21 @@ int run_bwd(const tg_attn_bwd_desc* d, hipStream_t st) {
   // statistics, then dQ: queries in registers, keys streamed
   p.r1 = d->q; p.r2 = d->dout; p.s1 = d->k; p.s2 = d->v; p.z1 = d->kt; p.z2 = d->kt;
   p.out1 = d->dq; p.out2 = nullptr;
-  launch_bwd<T, 2>(p, d->batch, st);
+  launch_hd<T, 2>(p, d->batch, st);
   TG_LAUNCH_CHECK();
-  launch_bwd<T, 0>(p, d->batch, st);
+  launch_hd<T, 0>(p, d->batch, st);
   TG_LAUNCH_CHECK();
   // dK, dV: keys in registers, queries streamed
   p.r1 = d->k; p.r2 = d->v; p.s1 = d->q; p.s2 = d->dout; p.z1 = d->qt; p.z2 = d->doutt;
   p.out1 = d->dk; p.out2 = d->dv;
-  launch_bwd<T, 1>(p, d->batch, st);
+  launch_hd<T, 1>(p, d->batch, st);
   TG_LAUNCH_CHECK();
   return TG_OK;
 }
 
 // cross-attention: the keys / values are constants of the conditioning — only dQ, over a short key set, optionally with the guidance term on the probabilities
 template <typename T>
-int run_bwd_cross(const tg_attn_bwd_cross_desc* d, hipStream_t st) {
+int run_cross(const tg_attn_bwd_cross_desc* d, hipStream_t st) {
   AttnBwdParams p{};
   p.heads = d->heads; p.hd = d->head_dim; p.n_r = d->n_q; p.n_s = d->n_k; p.n_z = (d->n_k + 7) & ~7; p.n_rblk = (d->n_q + 127) / 128;
   p.r_ld = p.o_ld = d->q_ld; p.r_bs = p.o_bs = d->q_bs;
@@ -320,41 +366,52 @@ int run_bwd_cross(const tg_attn_bwd_cross_desc* d, hipStream_t st) {
   p.scale = d->scale; p.scale_log2 = d->scale * 1.4426950408889634f; p.ds_scale = d->ds_scale;
   p.r1 = d->q; p.r2 = d->dout; p.s1 = d->k; p.s2 = d->v; p.z1 = d->kt; p.z2 = d->kt;
   p.out1 = d->dq; p.out2 = nullptr;
-  launch_bwd<T, 2>(p, d->batch, st);
+  launch_hd<T, 2>(p, d->batch, st);
   TG_LAUNCH_CHECK();
-  launch_bwd<T, 0>(p, d->batch, st);
+  launch_hd<T, 0>(p, d->batch, st);
   TG_LAUNCH_CHECK();
   return TG_OK;
 }
 
-}  // namespace
-
-extern "C" int tg_attention_bwd_cross(const tg_attn_bwd_cross_desc* d, void* stream) {
-  TG_CHECK(d != nullptr, TG_ERR_ARG, "tg_attention_bwd_cross: null descriptor");
-  TG_CHECK(d->dtype == TG_BF16 || d->dtype == TG_F16, TG_ERR_ARG, "tg_attention_bwd_cross: bad dtype");
-  TG_CHECK(d->batch > 0 && d->heads > 0 && d->n_q > 0 && d->n_k > 0, TG_ERR_ARG, "tg_attention_bwd_cross: empty problem");
-  TG_CHECK(d->head_dim > 0 && d->head_dim % 8 == 0 && d->head_dim <= 64, TG_ERR_UNSUPPORTED,
-           "tg_attention_bwd_cross: head_dim %d unsupported (multiple of 8, <= 64)", d->head_dim);
-  TG_CHECK(d->q && d->dout && d->k && d->v && d->kt && d->stats && d->dq, TG_ERR_ARG, "tg_attention_bwd_cross: null pointer");
-  TG_CHECK(d->q_ld % 8 == 0 && d->k_ld % 8 == 0 && d->t_ld % 8 == 0 && d->t_ld >= ((d->n_k + 7) & ~7), TG_ERR_ARG,
-           "tg_attention_bwd_cross: pitches must keep 16-byte alignment; the transposed keys are zero-padded to a multiple of 8 columns");
-  TG_CHECK(d->extra == nullptr || d->extra_ld >= d->n_k, TG_ERR_ARG, "tg_attention_bwd_cross: extra rows shorter than the key set");
+// validation + dispatch of the self / cross descriptors.  `fn` is the called entry point's name (it begins every message), (hd_lo, hd_hi] its own head-dim
+// window: the narrow entries keep refusing d > 64, the wide ones d <= 64
+int attention_bwd_self(const tg_attn_bwd_desc* d, void* stream, const char* fn, int hd_lo, int hd_hi) {
+  TG_CHECK(d != nullptr, TG_ERR_ARG, "%s: null descriptor", fn);
+  TG_CHECK(d->dtype == TG_BF16 || d->dtype == TG_F16, TG_ERR_ARG, "%s: bad dtype", fn);
+  TG_CHECK(d->batch > 0 && d->heads > 0 && d->n > 0, TG_ERR_ARG, "%s: empty problem", fn);
+  TG_CHECK(d->head_dim > hd_lo && d->head_dim <= hd_hi && d->head_dim % 8 == 0, TG_ERR_UNSUPPORTED,
+           "%s: head_dim %d unsupported (multiple of 8, %d < head_dim <= %d; the entry points without _wide take <= 64, the _wide ones the rest)", fn,
+           d->head_dim, hd_lo, hd_hi);
+  TG_CHECK(d->n % 8 == 0, TG_ERR_UNSUPPORTED, "%s: n (%d) must be a multiple of 8", fn, d->n);
+  TG_CHECK(d->q && d->k && d->v && d->dout && d->qt && d->kt && d->doutt && d->stats && d->dq && d->dk && d->dv, TG_ERR_ARG, "%s: null pointer", fn);
+  TG_CHECK(d->ld % 8 == 0 && d->t_ld % 8 == 0 && d->ld >= (int64_t)d->heads * d->head_dim && d->t_ld >= d->n, TG_ERR_ARG,
+           "%s: pitches must keep 16-byte alignment and cover the rows", fn);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->dtype == TG_BF16) return run_bwd_cross<bf16_t>(d, st);
-  return run_bwd_cross<f16_t>(d, st);
+  if (d->dtype == TG_BF16) return run_self<bf16_t>(d, st);
+  return run_self<f16_t>(d, st);
 }
 
-extern "C" int tg_attention_bwd(const tg_attn_bwd_desc* d, void* stream) {
-  TG_CHECK(d != nullptr, TG_ERR_ARG, "tg_attention_bwd: null descriptor");
-  TG_CHECK(d->dtype == TG_BF16 || d->dtype == TG_F16, TG_ERR_ARG, "tg_attention_bwd: bad dtype");
-  TG_CHECK(d->batch > 0 && d->heads > 0 && d->n > 0, TG_ERR_ARG, "tg_attention_bwd: empty problem");
-  TG_CHECK(d->head_dim > 0 && d->head_dim % 8 == 0 && d->head_dim <= 64, TG_ERR_UNSUPPORTED,
-           "tg_attention_bwd: head_dim %d unsupported (multiple of 8, <= 64)", d->head_dim);
-  TG_CHECK(d->n % 8 == 0, TG_ERR_UNSUPPORTED, "tg_attention_bwd: n (%d) must be a multiple of 8", d->n);
-  TG_CHECK(d->q && d->k && d->v && d->dout && d->qt && d->kt && d->doutt && d->stats && d->dq && d->dk && d->dv, TG_ERR_ARG, "tg_attention_bwd: null pointer");
-  TG_CHECK(d->ld % 8 == 0 && d->t_ld % 8 == 0 && d->ld >= (int64_t)d->heads * d->head_dim && d->t_ld >= d->n, TG_ERR_ARG,
-           "tg_attention_bwd: pitches must keep 16-byte alignment and cover the rows");
+int attention_bwd_cross(const tg_attn_bwd_cross_desc* d, void* stream, const char* fn, int hd_lo, int hd_hi) {
+  TG_CHECK(d != nullptr, TG_ERR_ARG, "%s: null descriptor", fn);
+  TG_CHECK(d->dtype == TG_BF16 || d->dtype == TG_F16, TG_ERR_ARG, "%s: bad dtype", fn);
+  TG_CHECK(d->batch > 0 && d->heads > 0 && d->n_q > 0 && d->n_k > 0, TG_ERR_ARG, "%s: empty problem", fn);
+  TG_CHECK(d->head_dim > hd_lo && d->head_dim <= hd_hi && d->head_dim % 8 == 0, TG_ERR_UNSUPPORTED,
+           "%s: head_dim %d unsupported (multiple of 8, %d < head_dim <= %d; the entry points without _wide take <= 64, the _wide ones the rest)", fn,
+           d->head_dim, hd_lo, hd_hi);
+  TG_CHECK(d->q && d->dout && d->k && d->v && d->kt && d->stats && d->dq, TG_ERR_ARG, "%s: null pointer", fn);
+  TG_CHECK(d->q_ld % 8 == 0 && d->k_ld % 8 == 0 && d->t_ld % 8 == 0 && d->t_ld >= ((d->n_k + 7) & ~7), TG_ERR_ARG,
+           "%s: pitches must keep 16-byte alignment; the transposed keys are zero-padded to a multiple of 8 columns", fn);
+  TG_CHECK(d->extra == nullptr || d->extra_ld >= d->n_k, TG_ERR_ARG, "%s: extra rows shorter than the key set", fn);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->dtype == TG_BF16) return run_bwd<bf16_t>(d, st);
-  return run_bwd<f16_t>(d, st);
+  if (d->dtype == TG_BF16) return run_cross<bf16_t>(d, st);
+  return run_cross<f16_t>(d, st);
+}
+
+}  // namespace
+
+extern "C" int tg_attention_bwd(const tg_attn_bwd_desc* d, void* stream) { return attention_bwd_self(d, stream, "tg_attention_bwd", 0, 64); }
+extern "C" int tg_attention_bwd_cross(const tg_attn_bwd_cross_desc* d, void* stream) { return attention_bwd_cross(d, stream, "tg_attention_bwd_cross", 0, 64); }
+extern "C" int tg_attention_bwd_wide(const tg_attn_bwd_desc* d, void* stream) { return attention_bwd_self(d, stream, "tg_attention_bwd_wide", 64, 160); }
+extern "C" int tg_attention_bwd_cross_wide(const tg_attn_bwd_cross_desc* d, void* stream) {
+  return attention_bwd_cross(d, stream, "tg_attention_bwd_cross_wide", 64, 160);
 }

@@ -162,6 +162,14 @@ int tg_gemm_plan(const tg_gemm_desc* d, int32_t* tile_m, int32_t* tile_n, int32_
  * of 64-pixel blocks per batch item (the `nblk` of tg_groupnorm_from_partials).  0: it cannot (ask before setting out_gn_partials). */
 int tg_gemm_gn_partial_blocks(const tg_gemm_desc* d);
 
+/* Second destination in a producer's epilogue (tg_rc_linear_dup, tg_conv_in_dup; copy: tg_dup_rows).  With classifier-free guidance the two halves of a UNet
+ * call, `torch.cat([latents] * 2)` (models/pipelines.py:411-414), are the same values with the same timestep until the first layer that reads
+ * encoder_hidden_states: that prefix is computed on ONE half of the batch, and the results the full batch consumes are stored twice by the kernel that
+ * produces them — every output element also goes to out[m * ldc + n + c_dup_offset], the same rounded value — so that both halves of one contiguous
+ * full-batch tensor exist without a copy pass (c_dup_offset = M * ldc).  c_dup_offset: elements, a positive multiple of 8, the second destination must not
+ * overlap the first; 0 = the plain entry point.  tg_gemm has no such variant: its callers copy (tg_dup_rows).
+ * Additive to ABI 308: new symbols only, no descriptor changes, TG_ABI_VERSION unchanged. */
+
 /* Upsample2D (nearest x2, then conv3x3 pad 1; models/unet_2d_blocks.py:620-622) with the upsampling FOLDED INTO THE WEIGHTS: the nine taps of output pixel
  * (2i + py, 2j + px) touch only a 2 x 2 block of input pixels, so every parity class cls = 2 py + px is a 2 x 2-tap conv on the low-resolution grid — 4/9 of
  * tg_gemm's multiply-adds for the same layer.  The descriptor is tg_gemm's: mode 1, upsample 1, stride 1, one source (a1 NULL) of c0 channels (c0 % 64 == 0),
@@ -310,6 +318,10 @@ int tg_geglu(int32_t dtype, const void* x, int64_t rows, int64_t inner, void* ou
 int tg_act(int32_t dtype, const void* x, int64_t n, int32_t act, void* out, void* stream);
 /* out = a + b (n elements; ControlNet residual injection, models/unet_2d_condition.py:938-946, 975-976) */
 int tg_add(int32_t dtype, const void* a, const void* b, int64_t n, void* out, void* stream);
+/* dst[r * cols + c] = src[r * ld + c] for r < rows, c < cols: a 16-byte vector copy of a (pitched) row block into a dense one — the fallback of the
+ * second-destination stores where the producing kernel cannot store twice (every tg_gemm kernel).  cols and ld multiples of 8 elements, ld >= cols, src / dst
+ * 16-byte aligned and not overlapping. */
+int tg_dup_rows(const void* src, void* dst, int64_t rows, int64_t cols, int64_t ld, int32_t dtype, void* stream);
 
 /* dst[b, c, r] = src[b, r, c]: NCHW <-> token-major conversion for the processors' 4-D input path
  * (attention_processor.py:318-320, 363-364) and ControlNet residual injection (models/unet_2d_condition.py:938-946). */
@@ -334,6 +346,12 @@ int tg_softmax_rows(int32_t dtype, const void* x, int64_t rows, int32_t cols, in
  */
 int tg_conv_in(int32_t dtype, const void* sample, int32_t src_dtype, int32_t batch, int32_t cin, int32_t h, int32_t w,
                const void* weight, const void* bias, int32_t cout, void* out, void* stream);
+/* tg_conv_in with a second destination (see "Second destination" above): every output row is also stored at out + dup_offset elements.  Only the matrix-core kernel stores
+ * twice: tg_conv_in_takes_dup(cin, cout) == 1 (cin = 4, cout a multiple of 160, cout <= 640; `out` 16-byte and `weight` 8-byte aligned at the call); any other
+ * problem with dup_offset != 0 is TG_ERR_ARG. */
+int tg_conv_in_dup(int32_t dtype, const void* sample, int32_t src_dtype, int32_t batch, int32_t cin, int32_t h, int32_t w,
+                   const void* weight, const void* bias, int32_t cout, void* out, int64_t dup_offset, void* stream);
+int tg_conv_in_takes_dup(int32_t cin, int32_t cout);
 int tg_conv_out(int32_t dtype, const void* x, int32_t batch, int32_t cin, int32_t h, int32_t w, const void* weight,
                 const void* bias, int32_t cout, void* out, int32_t out_f32, void* stream);
 /* round 5 (ABI 306): conv_norm_out + SiLU + conv_out in one launch (models/unet_2d_condition.py:1015-1018): x is the RAW block output, `coef` the
@@ -524,6 +542,8 @@ typedef struct {
   const float* u640;
 } tg_rc_linear_desc;
 int tg_rc_linear(const tg_rc_linear_desc* d, void* stream);
+/* tg_rc_linear with a second destination (see "Second destination" above): out[m * ldc + n + c_dup_offset] receives the same value; every instance stores twice. */
+int tg_rc_linear_dup(const tg_rc_linear_desc* d, int64_t c_dup_offset, void* stream);
 
 /* tg_rc_xattn: norm2 + attn2 (IPAttnProcessor / AttnProcessor cross-attention) + residual of a first-level BasicTransformerBlock in one
  * launch for SD-1.5's geometry (320 channels = 8 heads x 40, 77 text keys, 0 / 4 / 16 image keys):

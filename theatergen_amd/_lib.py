@@ -148,6 +148,7 @@ SIGNATURES = {
     "tg_groupnorm_coef": (i32, [i32, vp, vp, i32, i32, i32, i64, i32, f32, vp, vp, vp, vp, vp]),
     "tg_groupnorm_from_partials": (i32, [i32, vp, i32, i32, i64, i32, f32, vp, vp, i32, vp, vp, vp, i32, vp]),
     "tg_gemm_gn_partial_blocks": (i32, [C.POINTER(GemmDesc)]),
+    "tg_dup_rows": (i32, [vp, vp, i64, i64, i64, i32, vp]),
     "tg_conv_up2_eligible": (i32, [C.POINTER(GemmDesc)]),
     "tg_conv_up2": (i32, [C.POINTER(GemmDesc), vp]),
     "tg_geglu": (i32, [i32, vp, i64, i64, vp, vp]),
@@ -157,6 +158,8 @@ SIGNATURES = {
     "tg_conv1x1_nchw": (i32, [vp, i32, i32, i32, i64, vp, vp, f32, vp, vp]),
     "tg_softmax_rows": (i32, [i32, vp, i64, i32, i64, f32, vp, i64, vp]),
     "tg_conv_in": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
+    "tg_conv_in_dup": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i64, vp]),
+    "tg_conv_in_takes_dup": (i32, [i32, i32]),
     "tg_conv_out": (i32, [i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp]),
     "tg_conv_out_gn": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp]),
     "tg_conv_out_takes_coef": (i32, [i32, i32, i32, i32]),
@@ -184,6 +187,7 @@ SIGNATURES = {
     "tg_softmax_bwd_rows": (i32, [i32, vp, i32, i64, vp, i64, vp, i64, i64, i32, f32, vp, vp, i64, vp]),
     "tg_sumpool2x2": (i32, [i32, vp, i32, i32, i32, i32, vp, vp]),
     "tg_rc_linear": (i32, [C.POINTER(RcLinearDesc), vp]),
+    "tg_rc_linear_dup": (i32, [C.POINTER(RcLinearDesc), i64, vp]),
     "tg_rc_xattn": (i32, [C.POINTER(RcXattnDesc), vp]),
     "tg_rc_kv_pack": (i32, [i32, i32, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp]),
     "tg_rc_ff": (i32, [C.POINTER(RcFfDesc), vp]),
@@ -220,7 +224,11 @@ def lib():
         for name, (res, args) in SIGNATURES.items():
             if compat and not hasattr(h, name):
                 continue
-            fn = getattr(h, name)      # AttributeError if a declared symbol is not exported
+            try:
+                fn = getattr(h, name)
+            except AttributeError:     # a declared symbol is not exported: an older build of this ABI family (additive symbols keep the version)
+                raise RuntimeError(f"theatergen_amd: {LIB_PATH} (ABI version {got}) does not export {name}: "
+                                   "rebuild with `python -m theatergen_amd.build`") from None
             fn.restype = res
             fn.argtypes = args
         if got != ABI_VERSION and not compat:

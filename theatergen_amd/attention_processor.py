@@ -358,6 +358,25 @@ def _to_tokens(hidden_states):
     return hidden_states.contiguous().reshape(b * n, c), b, n, c, None
 
 
+_pair = None      # set by ``pair_output``: the next ``_finish`` writes its result into both halves of a dense [2 M, C] tensor
+
+
+class pair_output:
+    """``with pair_output() as got:`` — the ``_finish`` of the attention run inside (the CFG pair's attn1, on half the batch) allocates a dense [2 M, C]
+    tensor, has its to_out projection store every row into both halves (``ops`` ``pair_out``) and leaves it in ``got["full"]``; None when no ``_finish``
+    ran (a foreign processor) or its output was not token-major."""
+
+    def __enter__(self):
+        global _pair
+        self._prev, _pair = _pair, {"full": None}
+        return _pair
+
+    def __exit__(self, *exc):
+        global _pair
+        _pair = self._prev
+        return False
+
+
 def _finish(attn, o2d, B, N, C, shape4, x_tokens, fused_residual):
     """to_out projection (+bias) with the optional residual / rescale folded into the GEMM epilogue:
     ``(to_out(o) + residual) / rescale_output_factor`` (reference :358-369).  ``x_tokens`` is the token-major
@@ -366,10 +385,14 @@ def _finish(attn, o2d, B, N, C, shape4, x_tokens, fused_residual):
     if res is None and attn.residual_connection:
         res = x_tokens
     out = None
+    kw = {}
+    if _pair is not None and _pair["full"] is None and shape4 is None:
+        _pair["full"] = torch.empty((2 * o2d.shape[0], attn.to_out[0].weight.shape[0]), dtype=o2d.dtype, device=o2d.device)
+        kw = dict(pair_out=_pair["full"])
     if attn.rescale_output_factor == 1.0:
-        out = rowchain.linear320(o2d, attn.to_out[0].weight, attn.to_out[0].bias, res, attn, "to_out", _cached)
+        out = rowchain.linear320(o2d, attn.to_out[0].weight, attn.to_out[0].bias, res, attn, "to_out", _cached, **kw)
     if out is None:
-        out = ops.linear(o2d, attn.to_out[0].weight, attn.to_out[0].bias, res=res, out_scale=1.0 / attn.rescale_output_factor)
+        out = ops.linear(o2d, attn.to_out[0].weight, attn.to_out[0].bias, res=res, out_scale=1.0 / attn.rescale_output_factor, **kw)
     if shape4 is not None:
         b, c, h, w = shape4
         return ops.transpose(out, b, h * w, c).reshape(b, c, h, w)

@@ -406,7 +406,7 @@ __global__ __launch_bounds__(256) void conv_in_fast_kernel(const void* sample, i
 // channels at a time (5 accumulator tiles); bias, rounding, then a per-wave LDS bounce so that every store instruction covers 320-byte runs of pixel rows.
 template <typename T>
 __global__ __launch_bounds__(256) void conv_in_mfma_kernel(const void* sample, int src_dtype, int batch, int h, int w, const T* weight, const T* bias,
-                                                           int cout, T* out) {
+                                                           int cout, T* out, long dup) {
   typedef typename Vec<T>::v8 V8;
   typedef typename Vec<T>::v4 V4;
   constexpr int CIN = 4, K = 36, KP = 48, WP = 56, OP = 168;        // LDS pitches (elements): weight rows 112 B, bounce rows 336 B
@@ -476,7 +476,10 @@ __global__ __launch_bounds__(256) void conv_in_mfma_kernel(const void* sample, i
       for (int it = 0; it < 10; ++it) {
         const int q = it * 64 + lane, px = q / 20, cn = q - px * 20;
         const V8 v = *reinterpret_cast<const V8*>(so + px * OP + cn * 8);
-        if (base + px < npix) *reinterpret_cast<V8*>(out + (base + px) * cout + half * 160 + cn * 8) = v;
+        if (base + px < npix) {
+          *reinterpret_cast<V8*>(out + (base + px) * cout + half * 160 + cn * 8) = v;
+          if (dup != 0) *reinterpret_cast<V8*>(out + (base + px) * cout + half * 160 + cn * 8 + dup) = v;     // tg_conv_in_dup (wave-uniform)
+        }
       }
       __builtin_amdgcn_wave_barrier();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -767,16 +770,65 @@ extern "C" int tg_add(int32_t dtype, const void* a, const void* b, int64_t n, vo
   return TG_OK;
 }
 
+namespace {
+// the matrix-core conv_in kernel takes the channel counts (dev A/B knob TG_CONV_IN_MFMA=0: the fp32-FMA kernels)
+bool conv_in_mfma_ok(int cin, int cout) {
+  static const bool mfma_on = [] { const char* e = getenv("TG_CONV_IN_MFMA"); return !(e && e[0] == '0'); }();
+  return mfma_on && cin == 4 && cout > 0 && cout % 160 == 0 && cout <= 640;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void dup_rows_kernel(const T* src, T* dst, long rows, int cols8, long ld) {
+  typedef typename Vec<T>::v8 V8;
+  const long n = rows * cols8;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long r = i / cols8;
+    const int c = (int)(i - r * cols8);
+    *reinterpret_cast<V8*>(dst + (r * cols8 + c) * 8) = *reinterpret_cast<const V8*>(src + r * ld + c * 8);
+  }
+}
+}  // namespace
+
+extern "C" int tg_dup_rows(const void* src, void* dst, int64_t rows, int64_t cols, int64_t ld, int32_t dtype, void* stream) {
+  TG_CHECK((dtype == TG_BF16 || dtype == TG_F16) && src && dst && rows > 0 && cols > 0, TG_ERR_ARG, "tg_dup_rows: bad args");
+  TG_CHECK(cols % 8 == 0 && ld % 8 == 0 && ld >= cols && cols < (1LL << 31), TG_ERR_ARG, "tg_dup_rows: cols = %lld and ld = %lld must be multiples of 8 with ld >= cols",
+           (long long)cols, (long long)ld);
+  TG_CHECK((reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0, TG_ERR_ARG, "tg_dup_rows: src / dst must be 16-byte aligned");
+  {
+    const char* s0 = reinterpret_cast<const char*>(src);
+    const char* d0 = reinterpret_cast<const char*>(dst);
+    const long sb = ((rows - 1) * ld + cols) * 2, db = rows * cols * 2;
+    TG_CHECK(s0 + sb <= d0 || d0 + db <= s0, TG_ERR_ARG, "tg_dup_rows: src and dst overlap");
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int grid = grid_for(rows * cols, 8);
+  if (dtype == TG_BF16) hipLaunchKernelGGL(dup_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, (long)rows, (int)(cols / 8), (long)ld);
+  else hipLaunchKernelGGL(dup_rows_kernel<f16_t>, dim3(grid), dim3(256), 0, st, (const f16_t*)src, (f16_t*)dst, (long)rows, (int)(cols / 8), (long)ld);
+  TG_LAUNCH_CHECK();
+  return TG_OK;
+}
+
+extern "C" int tg_conv_in_takes_dup(int32_t cin, int32_t cout) { return conv_in_mfma_ok(cin, cout) ? 1 : 0; }
+
 extern "C" int tg_conv_in(int32_t dtype, const void* sample, int32_t src_dtype, int32_t batch, int32_t cin, int32_t h,
                           int32_t w, const void* weight, const void* bias, int32_t cout, void* out, void* stream) {
+  return tg_conv_in_dup(dtype, sample, src_dtype, batch, cin, h, w, weight, bias, cout, out, 0, stream);
+}
+
+extern "C" int tg_conv_in_dup(int32_t dtype, const void* sample, int32_t src_dtype, int32_t batch, int32_t cin, int32_t h,
+                              int32_t w, const void* weight, const void* bias, int32_t cout, void* out, int64_t dup_offset, void* stream) {
   TG_CHECK((dtype == TG_BF16 || dtype == TG_F16) && sample && weight && out, TG_ERR_ARG, "tg_conv_in: bad args");
   TG_CHECK(src_dtype >= 0 && src_dtype <= 2 && batch > 0 && cin > 0 && cin <= 16 && cout > 0, TG_ERR_ARG, "tg_conv_in: bad shape");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const long npix = (long)batch * h * w;
   {
     // matrix-core path (round 5): cin = 4, cout a multiple of 160 (dev A/B knob TG_CONV_IN_MFMA=0: the fp32-FMA kernels below)
-    static const bool mfma_on = [] { const char* e = getenv("TG_CONV_IN_MFMA"); return !(e && e[0] == '0'); }();
-    if (mfma_on && cin == 4 && cout % 160 == 0 && cout <= 640 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(weight) & 7) == 0) {
+    const bool mfma = conv_in_mfma_ok(cin, cout) && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(weight) & 7) == 0;
+    // the second store exists in the matrix-core kernel only: never ignored elsewhere
+    TG_CHECK(dup_offset == 0 || (mfma && dup_offset % 8 == 0 && dup_offset >= npix * cout), TG_ERR_ARG,
+             "tg_conv_in_dup: dup_offset = %lld needs the matrix-core kernel (tg_conv_in_takes_dup, aligned out / weight) and a multiple of 8 past the first destination",
+             (long long)dup_offset);
+    if (mfma) {
       const size_t lds = ((size_t)cout * 56 + 4 * 32 * 168) * 2;
       long nb = (npix + 127) / 128;
       if (nb > 1024) nb = 1024;
@@ -784,12 +836,12 @@ extern "C" int tg_conv_in(int32_t dtype, const void* sample, int32_t src_dtype, 
         auto k = conv_in_mfma_kernel<bf16_t>;
         static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)attr;
-        hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(256), lds, st, sample, src_dtype, batch, h, w, (const bf16_t*)weight, (const bf16_t*)bias, cout, (bf16_t*)out);
+        hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(256), lds, st, sample, src_dtype, batch, h, w, (const bf16_t*)weight, (const bf16_t*)bias, cout, (bf16_t*)out, (long)dup_offset);
       } else {
         auto k = conv_in_mfma_kernel<f16_t>;
         static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)attr;
-        hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(256), lds, st, sample, src_dtype, batch, h, w, (const f16_t*)weight, (const f16_t*)bias, cout, (f16_t*)out);
+        hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(256), lds, st, sample, src_dtype, batch, h, w, (const f16_t*)weight, (const f16_t*)bias, cout, (f16_t*)out, (long)dup_offset);
       }
       TG_LAUNCH_CHECK();
       return TG_OK;

@@ -53,6 +53,7 @@ struct RcLinearParams {
   int N, K;
   float ln_eps;
   int dbg;            // dev timing experiments (variant >> 8): 1 no stores, 2 no chunk DMA after the first, 4 no barrier, 8 no MFMA loop
+  long c_dup;         // tg_rc_linear_dup: every output row is stored again c_dup elements further on, 0 = off
 };
 
 // Workgroup -> row block, XCD-aware (speed only): the dispatcher places block b on XCD b % 8 and every XCD has a private L2.  The LDS-tiled
@@ -220,6 +221,11 @@ __global__ __launch_bounds__(NW * 64) void rc_linear_kernel(RcLinearParams p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         if (mok[i]) *reinterpret_cast<V8*>(outp + mrow[i] * p.ldc + pend_ch + 8 * qb) = pend[i];
+      if (p.c_dup != 0) {                      // wave-uniform: the second destination of tg_rc_linear_dup
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (mok[i]) *reinterpret_cast<V8*>(outp + mrow[i] * p.ldc + pend_ch + 8 * qb + p.c_dup) = pend[i];
+      }
     }
     const long ch0 = 64 * (long)c + 32 * hi;
     V8 r8[4];
@@ -299,6 +305,11 @@ __global__ __launch_bounds__(NW * 64) void rc_linear_kernel(RcLinearParams p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if (mok[i]) *reinterpret_cast<V8*>(outp + mrow[i] * p.ldc + pend_ch + 8 * qb) = pend[i];
+    if (p.c_dup != 0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (mok[i]) *reinterpret_cast<V8*>(outp + mrow[i] * p.ldc + pend_ch + 8 * qb + p.c_dup) = pend[i];
+    }
   }
 }
 
@@ -1491,7 +1502,9 @@ inline bool rc_dev_enabled() {
 
 }  // namespace
 
-extern "C" int tg_rc_linear(const tg_rc_linear_desc* d, void* stream) {
+extern "C" int tg_rc_linear(const tg_rc_linear_desc* d, void* stream) { return tg_rc_linear_dup(d, 0, stream); }
+
+extern "C" int tg_rc_linear_dup(const tg_rc_linear_desc* d, int64_t c_dup_offset, void* stream) {
   TG_CHECK(d != nullptr, TG_ERR_ARG, "tg_rc_linear: null descriptor");
   TG_CHECK(d->dtype == TG_BF16 || d->dtype == TG_F16, TG_ERR_ARG, "tg_rc_linear: dtype %d", d->dtype);
   TG_CHECK(d->K == 320, TG_ERR_ARG, "tg_rc_linear: K = %d (320: the token row lives in registers; the K = 640 variant of round 4 was removed)", d->K);
@@ -1500,7 +1513,10 @@ extern "C" int tg_rc_linear(const tg_rc_linear_desc* d, void* stream) {
   TG_CHECK(d->M > 0 && d->x && d->wpk && d->out, TG_ERR_ARG, "tg_rc_linear: null operand or M <= 0");
   TG_CHECK(d->ldx >= d->K && d->ldx % 8 == 0 && d->ldc >= d->N && d->ldc % 8 == 0, TG_ERR_ARG, "tg_rc_linear: row pitches must be multiples of 8 elements");
   TG_CHECK(!d->res || (d->ldres >= d->N && d->ldres % 8 == 0), TG_ERR_ARG, "tg_rc_linear: residual pitch");
+  TG_CHECK(c_dup_offset == 0 || (c_dup_offset % 8 == 0 && c_dup_offset >= (d->M - 1) * d->ldc + d->N), TG_ERR_ARG,
+           "tg_rc_linear_dup: c_dup_offset = %lld must be a multiple of 8 elements past the first destination", (long long)c_dup_offset);
     RcLinearParams p;
+  p.c_dup = (long)c_dup_offset;
   p.x = d->x; p.ldx = d->ldx; p.wpk = d->wpk; p.res = d->res; p.ldres = d->ldres;
   p.out = d->out; p.ldc = d->ldc; p.M = d->M; p.N = d->N; p.K = d->K; p.ln_eps = d->ln_eps; p.dbg = d->variant >> 8;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);

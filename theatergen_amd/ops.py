@@ -69,10 +69,16 @@ def workspace(nbytes, device):
 def gemm(a0, w, M, N, K, *, mode=0, a1=None, c0=None, c1=0, conv=None, bias=None, bvec=None, rows_per_batch=0,
          res=None, act=ACT_NONE, out_scale=1.0, out=None, n_split=0, out_t=None, ldt=0, force_split_k=0, force_tile=0,
          a_rows_per_batch=0, a_batch_stride=0, geglu=False, pad_mode=0, a_coef=None, a_silu=False, plan_only=False, ln=None, lda=0, ldw=0,
-         gn_out=None):
+         gn_out=None, pair_out=None):
     """out[M, N] = epilogue(A[M, K] @ W[N, K]^T); see tg_gemm in include/theatergen_hip.h.
-    ``conv`` = (batch, in_h, in_w, out_h, out_w, stride, upsample) for mode 1."""
+    ``conv`` = (batch, in_h, in_w, out_h, out_w, stride, upsample) for mode 1.
+    ``pair_out`` (dense [2 M, N]): the result goes to its rows [0, M) and, by one ``dup_rows`` copy, to [M, 2 M) (no tg_gemm kernel stores twice: the
+    slab conv has no registers to spare for it); returns ``pair_out[:M]``."""
     _need_cuda(a0)
+    if pair_out is not None:
+        if out is not None or n_split > 0 or geglu or pair_out.shape != (2 * M, N) or not pair_out.is_contiguous() or pair_out.dtype != a0.dtype:
+            raise RuntimeError("gemm: pair_out must be the only output, a dense [2 M, N] tensor of the activation dtype")
+        out = pair_out[:M]
     L = _lib.lib()
     d = GemmDesc()
     d.dtype = _dt(a0)
@@ -136,15 +142,19 @@ def gemm(a0, w, M, N, K, *, mode=0, a1=None, c0=None, c1=0, conv=None, bias=None
         ws = workspace(need, a0.device)
         d.workspace = ws.data_ptr()
         d.workspace_bytes = ws.numel() * 4
-    if _gemm_profile is None:
+    def launch():
         _lib.check(L.tg_gemm(C.byref(d), _stream()))
+        if pair_out is not None:
+            dup_rows(out, pair_out[M:])
+    if _gemm_profile is None:
+        launch()
         return out
     # profiling mode (bench.py roofline leg): HIP events on the launch stream around this one launch
     tm, tn, sp, kk = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
     _lib.check(L.tg_gemm_plan(C.byref(d), C.byref(tm), C.byref(tn), C.byref(sp), C.byref(kk)))
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    _lib.check(L.tg_gemm(C.byref(d), _stream()))
+    launch()
     e1.record()
     if kk.value == 2:
         kname = "conv_halo_kernel<128x128>"
@@ -211,12 +221,28 @@ def linear(x, w, bias=None, **kw):
     return gemm(x, w, M, N, K, bias=bias, **kw)
 
 
-def rc_linear(x, wpk, N, *, res=None, ln_eps=None, out=None, variant=0):
+def dup_rows(src, dst):
+    """dst (dense [rows, cols]) = src ([rows, cols], any row pitch): ``tg_dup_rows``, the copy behind ``pair_out`` where a producer cannot store twice"""
+    _need_cuda(src)
+    rows, cols = src.shape
+    if src.stride(1) != 1 or dst.shape != src.shape or not dst.is_contiguous() or dst.dtype != src.dtype:
+        raise RuntimeError("dup_rows: src [rows, cols] with unit column stride, dst a dense tensor of the same shape and dtype")
+    _lib.check(_lib.lib().tg_dup_rows(_ptr(src), _ptr(dst), int(rows), int(cols), int(src.stride(0)), _dt(src), _stream()))
+    return dst
+
+
+def rc_linear(x, wpk, N, *, res=None, ln_eps=None, out=None, variant=0, pair_out=None):
     """Row-chain projection (csrc/tg_rowchain.hip): out = [LayerNorm-folded] x @ W^T + v (+ res) with the token rows in registers;
-    ``wpk`` = ``weights_pack.rc_pack(W, v, u)`` (uint8 chunk stream), x [M, 320]."""
+    ``wpk`` = ``weights_pack.rc_pack(W, v, u)`` (uint8 chunk stream), x [M, 320].  ``pair_out`` (dense [2 M, N]): both halves receive the
+    result from the kernel's epilogue (``tg_rc_linear_dup``); returns ``pair_out[:M]``."""
     from ._lib import RcLinearDesc
     _need_cuda(x)
     M, K = x.shape
+    if pair_out is not None:
+        if out is not None or pair_out.shape != (2 * M, N) or not pair_out.is_contiguous() or pair_out.dtype != x.dtype:
+            raise RuntimeError("rc_linear: pair_out must be the only output, a dense [2 M, N] tensor of the activation dtype")
+        out = pair_out[:M]
+    dup = int(M) * int(N) if pair_out is not None else 0
     assert x.stride(1) == 1 and wpk.dtype == torch.uint8
     if K != 320:
         raise RuntimeError(f"rc_linear: K = {K} (the row-chain projection keeps a 320-channel token row in registers)")
@@ -231,7 +257,8 @@ def rc_linear(x, wpk, N, *, res=None, ln_eps=None, out=None, variant=0):
     d.M, d.N, d.K = int(M), int(N), int(K)
     d.ln, d.ln_eps = (1, float(ln_eps)) if ln_eps is not None else (0, 0.0)
     d.variant = int(variant)
-    _profiled(lambda: _lib.check(_lib.lib().tg_rc_linear(C.byref(d), _stream())), "rc_linear_kernel<320>" + ("+ln" if ln_eps is not None else ""),
+    _profiled(lambda: _lib.check(_lib.lib().tg_rc_linear_dup(C.byref(d), dup, _stream()) if dup else _lib.lib().tg_rc_linear(C.byref(d), _stream())),
+              "rc_linear_kernel<320>" + ("+ln" if ln_eps is not None else ""),
               M, N, K, 2.0 * M * N * K, res is not None)
     return out
 
@@ -726,11 +753,22 @@ def softmax_rows(x, scale=1.0, out=None):
 _SRC = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}
 
 
-def conv_in(sample, weight_packed, bias, cout, dtype):
-    """sample NCHW (bf16/f16/f32) -> token-major [B*h*w, cout] in ``dtype``"""
+def conv_in(sample, weight_packed, bias, cout, dtype, pair=False):
+    """sample NCHW (bf16/f16/f32) -> token-major [B*h*w, cout] in ``dtype``.  ``pair``: the caller vouches that sample[:B/2] and sample[B/2:] hold the same
+    values — the conv runs on the first half and both halves of the output are written (``tg_conv_in_dup``, or one ``dup_rows`` copy)."""
     _need_cuda(sample)
     B, cin, h, w = sample.shape
     out = torch.empty((B * h * w, cout), dtype=dtype, device=sample.device)
+    if pair:
+        L = _lib.lib()
+        hb, rows = B // 2, (B // 2) * h * w
+        if L.tg_conv_in_takes_dup(cin, cout) and out.data_ptr() % 16 == 0 and weight_packed.data_ptr() % 8 == 0:
+            _lib.check(L.tg_conv_in_dup(_dt(out), _ptr(sample), _SRC[sample.dtype], hb, cin, h, w, _ptr(weight_packed), _ptr(bias), cout, _ptr(out),
+                                        rows * cout, _stream()))
+        else:
+            _lib.check(L.tg_conv_in(_dt(out), _ptr(sample), _SRC[sample.dtype], hb, cin, h, w, _ptr(weight_packed), _ptr(bias), cout, _ptr(out), _stream()))
+            dup_rows(out[:rows], out[rows:])
+        return out
     _lib.check(_lib.lib().tg_conv_in(_dt(out), _ptr(sample), _SRC[sample.dtype], B, cin, h, w, _ptr(weight_packed), _ptr(bias),
                                      cout, _ptr(out), _stream()))
     return out

@@ -240,7 +240,7 @@ class DenoiseEngine:
             down = self.adapter_feats                                          # T2I-Adapter mode: mid stays None
         noise_pred = self.unet(self.model_in, self.sched, self.enc, added_cond_kwargs=self.added, return_dict=False,
                                out_dtype=torch.float32, down_block_additional_residuals=down,
-                               mid_block_additional_residual=mid, time_proj=tp)[0]
+                               mid_block_additional_residual=mid, time_proj=tp, shared_pair=self.added is None)[0]
         if self.kind != "ddim":
             ops.step_epilogue_sigma(noise_pred, self.latents, self.g, self.coef, self.step_idx, advance=True, noise=self.step_noise,
                                     frozen=self.frozen, frozen_mask=self.frozen_mask, frozen_steps=self.frozen_steps, history=self.history,

@@ -102,7 +102,7 @@ def pack_xattn_out(wo, bo):
     return rc_pack_tiles(w2, bo.detach().float() if bo is not None else None)
 
 
-def linear320(x2d, lin_weight, bias, res, owner, name, cached):
+def linear320(x2d, lin_weight, bias, res, owner, name, cached, pair_out=None):
     """``x @ W^T + b (+ res)`` through ``tg_rc_linear`` when the shape pays — K = 320, rows >= MIN_ROWS_CHAIN, N % 64 == 0 —, else None.
     ``cached(owner, name, tensors, build)`` is the caller's packed-weight cache."""
     M, K = x2d.shape
@@ -113,7 +113,7 @@ def linear320(x2d, lin_weight, bias, res, owner, name, cached):
     if K == 320 and (MODE & 1) and N % 64 == 0 and M >= MIN_ROWS_CHAIN:
         trace("linear320 yes", name, M, N)
         wpk = cached(owner, "rc_" + name, ts, lambda: rc_pack(lin_weight.detach(), bias.detach().float() if bias is not None else None))
-        return ops.rc_linear(x2d, wpk, N, res=res)
+        return ops.rc_linear(x2d, wpk, N, res=res, pair_out=pair_out)
     trace("linear_rc no", name, M, K, N)
     return None
 

@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import ops
 from . import rowchain
 from .attention_processor import (tensor_version, Attention, AttnProcessor, CNAttnProcessor, IPAttnProcessor, _cached, front_eligible, fused_cross_block,
-                                  ln_weight, self_attention_from_qkv)
+                                  ln_weight, pair_output, self_attention_from_qkv)
 from .config import UNetConfig
 from .weights_pack import pack_conv1x1, pack_conv3x3, pack_conv3x3_up2, pack_geglu, pack_ln_linear, rc_pack_tiles
 
@@ -130,8 +130,12 @@ class ResnetBlock2D(nn.Module):
         self._p = _Packed()
         self.temb_slot = None      # (offset, width) into the fused time-projection output, set by the UNet
 
-    def run(self, x: _Act, skip: _Act, tproj):
-        """x (+ skip = channel concat) -> _Act.  ``tproj`` = fused time projections [B, sum(cout)]."""
+    def run(self, x: _Act, skip: _Act, tproj, pair=False, pair_src=None):
+        """x (+ skip = channel concat) -> _Act.  ``tproj`` = fused time projections [B, sum(cout)].
+        ``pair``: x is one half of a CFG pair -> (the half-batch _Act, the full-batch _Act both of whose halves hold conv2's output).
+        ``pair_src`` (with ``pair``): the full-batch _Act of which x is the first half.  norm1's statistics launch cuts every image into 512 / batch
+        pixel slabs (csrc/tg_norm.hip: gn_nblk), so on half the batch it would sum in another order; it runs on the full tensor instead — the plan
+        and the bits of the unshared call — and the first half of its coefficients is used."""
         c1 = skip.c if skip is not None else 0
         assert x.c + c1 == self.in_channels
         w1 = self._p.get("c1", [self.conv1.weight], lambda: pack_conv3x3(self.conv1.weight.detach()))
@@ -150,8 +154,12 @@ class ResnetBlock2D(nn.Module):
             kw1.update(gn_out=gn1)
         if _FUSE_GN and ops.conv3x3_takes_gn(x.t.dtype, x.b, x.h, x.w, x.c, c1, self.out_channels):
             g0 = _gn_of(x.gn, self.groups) if skip is None else None
-            coef = (ops.groupnorm_from_partials(g0, x.b, x.hw, x.c, self.eps, self.norm1.weight, self.norm1.bias) if g0 is not None else
-                    ops.groupnorm_coef(x.t, x.b, x.hw, self.groups, self.eps, self.norm1.weight, self.norm1.bias, x1=x1))
+            if g0 is not None:
+                coef = ops.groupnorm_from_partials(g0, x.b, x.hw, x.c, self.eps, self.norm1.weight, self.norm1.bias)
+            elif pair_src is not None and skip is None:
+                coef = ops.groupnorm_coef(pair_src.t, pair_src.b, x.hw, self.groups, self.eps, self.norm1.weight, self.norm1.bias)[:x.b]
+            else:
+                coef = ops.groupnorm_coef(x.t, x.b, x.hw, self.groups, self.eps, self.norm1.weight, self.norm1.bias, x1=x1)
             h = ops.conv3x3(x.t, w1, x.b, x.h, x.w, x.c, x1=x1, c1=c1, a_coef=coef, a_silu=True, **kw1)
         else:
             h = ops.groupnorm(x.t, x.b, x.hw, self.groups, self.eps, self.norm1.weight, self.norm1.bias, silu=True, x1=x1)
@@ -163,6 +171,9 @@ class ResnetBlock2D(nn.Module):
         else:
             res = x.t
         kw2 = dict(bias=self.conv2.bias, res=res, out_scale=1.0 / self.output_scale_factor)
+        full = torch.empty((2 * x.b * x.hw, self.out_channels), dtype=x.t.dtype, device=x.t.device) if pair else None
+        if pair:
+            kw2.update(pair_out=full)
         gn2 = {"groups": self.groups} if _GN_EPI else None                 # conv2 -> the next GroupNorm(groups) of the block output (Transformer2DModel.norm)
         if gn2 is not None:
             kw2.update(gn_out=gn2)
@@ -174,7 +185,10 @@ class ResnetBlock2D(nn.Module):
         else:
             h = ops.groupnorm(h, x.b, x.hw, self.groups, self.eps, self.norm2.weight, self.norm2.bias, silu=True)
             out = ops.conv3x3(h, w2, x.b, x.h, x.w, self.out_channels, **kw2)
-        return _Act(out, x.b, x.h, x.w, self.out_channels, gn=_gn_of(gn2, self.groups))
+        half = _Act(out, x.b, x.h, x.w, self.out_channels, gn=_gn_of(gn2, self.groups))
+        if pair:
+            return half, _Act(full, 2 * x.b, x.h, x.w, self.out_channels)      # the partials describe the half batch only: the full view carries none
+        return half
 
 
 class Downsample2D(nn.Module):
@@ -191,6 +205,11 @@ class Downsample2D(nn.Module):
         kw = {} if res is None else dict(res=res)
         out = ops.conv3x3(x.t, w, x.b, x.h, x.w, x.c, stride=2, bias=self.conv.bias, **kw)
         return _Act(out, x.b, (x.h - 1) // 2 + 1, (x.w - 1) // 2 + 1, x.c)
+
+
+# CFG pair prefix: with ``forward(shared_pair=True)`` conv_in, down_blocks[0].resnets[0] and the first transformer's front + attn1 run on half the batch
+# and their producers store both halves (ops ``pair_out``).  TG_CFG_SHARE=0 (dev A/B) = off.
+_CFG_SHARE = os.environ.get("TG_CFG_SHARE", "1") != "0"
 
 
 # Upsample2D on tg_conv_up2 (nearest x2 folded into the weights: four 2x2-tap convs, 4/9 of the MFMAs) where the kernel takes the layer.  TG_UP_FOLD=0 (dev A/B) = off.
@@ -329,11 +348,28 @@ class BasicTransformerBlock(nn.Module):
             out = out[0]
         return ops.add(out.reshape(b * n, -1).contiguous(), residual)
 
-    def run(self, x2d, b, n, enc, ca_kwargs, tail=None, pre_qkv=None):
+    def _attn1_pair(self, fn, x2d):
+        """run attn1 (``fn``) on the half batch ``x2d`` and return its output for BOTH halves, dense [2 M, C]: written twice by the to_out
+        projection's epilogue where our processors end in ``_finish``, else (foreign processor) by two copies"""
+        with pair_output() as got:
+            h = fn()
+        if got["full"] is not None:
+            return got["full"]
+        full = torch.empty((2 * h.shape[0], h.shape[1]), dtype=h.dtype, device=h.device)
+        ops.dup_rows(h, full[:h.shape[0]])
+        ops.dup_rows(h, full[h.shape[0]:])
+        return full
+
+    def run(self, x2d, b, n, enc, ca_kwargs, tail=None, pre_qkv=None, pair=False):
         """``tail`` (optional, from ``Transformer2DModel``: (packed proj_out weight, bias, residual)) — when the fused feed-forward launch
         takes it, the block returns ``(proj_out output, True)``; otherwise a plain tensor (the caller runs proj_out itself).
-        ``pre_qkv`` = (Q | K, V^T, ldt) of norm1(x2d) already projected by ``tg_rc_front``."""
+        ``pre_qkv`` = (Q | K, V^T, ldt) of norm1(x2d) already projected by ``tg_rc_front``.
+        ``pair``: x2d / b are ONE half of a CFG pair whose halves are equal up to here; attn1 runs on it, everything from attn2 on (the first
+        reader of ``enc``) on the full batch 2 b."""
         M, C = x2d.shape
+        one = (lambda fn, t: self._attn1_pair(fn, t)) if pair else (lambda fn, t: fn())
+        bf = 2 * b if pair else b
+        M = 2 * M if pair else M                       # the path is chosen for the rows attn2 and the feed-forward see: the same launches as without sharing
         if _LN_MODE and M >= _FUSE_LN_MIN_ROWS and C % 64 == 0 and x2d.stride(0) == C:
             # LayerNorm rides in the projection that consumes it (tg_gemm ln_u / ln_v): no normalised tensor.  Row statistics: a
             # statistics-only pass (half the layernorm kernel's traffic) or taken inside the GEMM from its own A tiles
@@ -343,17 +379,17 @@ class BasicTransformerBlock(nn.Module):
                 return (norm, ops.layernorm_stats(t, norm.eps) if (_LN_MODE & 4 or _pp_takes_ln(t.shape[0], n_out, t.shape[1])) else None)
             if _LN_MODE & 1:
                 if pre_qkv is not None:
-                    x2d = self_attention_from_qkv(self.attn1, pre_qkv[0], pre_qkv[1], pre_qkv[2], b, n, x2d)
+                    x2d = one(lambda: self_attention_from_qkv(self.attn1, pre_qkv[0], pre_qkv[1], pre_qkv[2], b, n, x2d), x2d)
                 else:
-                    x2d = self._call(self.attn1, x2d, b, n, None, x2d, ca_kwargs, ln=folded(self.norm1, x2d, 3 * self.attn1.to_q.weight.shape[0]))
+                    x2d = one(lambda: self._call(self.attn1, x2d, b, n, None, x2d, ca_kwargs, ln=folded(self.norm1, x2d, 3 * self.attn1.to_q.weight.shape[0])), x2d)
                 # first level of SD-1.5: norm2 + attn2 + residual as ONE row-chain launch (q, scores and O stay in registers)
-                h2 = fused_cross_block(self.attn2, self.norm2, x2d, b, n, enc, ca_kwargs)
-                x2d = h2 if h2 is not None else self._call(self.attn2, x2d, b, n, enc, x2d, ca_kwargs, ln=folded(self.norm2, x2d))
+                h2 = fused_cross_block(self.attn2, self.norm2, x2d, bf, n, enc, ca_kwargs)
+                x2d = h2 if h2 is not None else self._call(self.attn2, x2d, bf, n, enc, x2d, ca_kwargs, ln=folded(self.norm2, x2d))
             else:
                 h = ops.layernorm(x2d, self.norm1.weight, self.norm1.bias, self.norm1.eps)
-                x2d = self._call(self.attn1, h, b, n, None, x2d, ca_kwargs)
+                x2d = one(lambda: self._call(self.attn1, h, b, n, None, x2d, ca_kwargs), x2d)
                 h = ops.layernorm(x2d, self.norm2.weight, self.norm2.bias, self.norm2.eps)
-                x2d = self._call(self.attn2, h, b, n, enc, x2d, ca_kwargs)
+                x2d = self._call(self.attn2, h, bf, n, enc, x2d, ca_kwargs)
             fused = self.ff.run_fused(x2d, self.norm3, tail)
             if fused is not None:
                 return (fused, True) if tail is not None else fused
@@ -362,9 +398,9 @@ class BasicTransformerBlock(nn.Module):
             h = ops.layernorm(x2d, self.norm3.weight, self.norm3.bias, self.norm3.eps)
             return self.ff.run(h, x2d)
         h = ops.layernorm(x2d, self.norm1.weight, self.norm1.bias, self.norm1.eps)
-        x2d = self._call(self.attn1, h, b, n, None, x2d, ca_kwargs)
+        x2d = one(lambda: self._call(self.attn1, h, b, n, None, x2d, ca_kwargs), x2d)
         h = ops.layernorm(x2d, self.norm2.weight, self.norm2.bias, self.norm2.eps)
-        x2d = self._call(self.attn2, h, b, n, enc, x2d, ca_kwargs)
+        x2d = self._call(self.attn2, h, bf, n, enc, x2d, ca_kwargs)
         h = ops.layernorm(x2d, self.norm3.weight, self.norm3.bias, self.norm3.eps)
         return self.ff.run(h, x2d)
 
@@ -412,7 +448,11 @@ class Transformer2DModel(nn.Module):
         wqkv = self._p.get("rc_front_qkv", [wl, ul, vl], lambda: rc_pack_tiles(wl, vl, ul))
         return ops.rc_front(x.t, coef, win, wqkv, x.hw, blk.norm1.eps)
 
-    def run(self, x: _Act, enc, ca_kwargs):
+    def run(self, x: _Act, enc, ca_kwargs, pair_full=None):
+        """``pair_full`` (the full-batch _Act of which ``x`` is one half, CFG pair): the front and the first block's attn1 run on ``x``, the rest — and
+        proj_out's residual — on the full batch; returns the full-batch _Act."""
+        pair = pair_full is not None
+        xr = pair_full if pair else x                   # what proj_out's residual and the output geometry come from
         w_in = self._w("in", self.proj_in)
         pre = self._front(x, w_in, ca_kwargs)
         if pre is not None:
@@ -429,14 +469,14 @@ class Transformer2DModel(nn.Module):
         for i, blk in enumerate(self.transformer_blocks):
             if base_key is not None:
                 ca_kwargs["attn_key"] = base_key + [i]           # transformer_2d.py:299-304
-            y = blk.run(y, x.b, x.hw, enc, ca_kwargs, tail=(w_out, self.proj_out.bias, x.t) if i == last else None,
-                        pre_qkv=pre if i == 0 else None)
+            y = blk.run(y, x.b if (pair and i == 0) else xr.b, x.hw, enc, ca_kwargs, tail=(w_out, self.proj_out.bias, xr.t) if i == last else None,
+                        pre_qkv=pre if i == 0 else None, pair=pair and i == 0)
             if isinstance(y, tuple):                             # the last block's fused feed-forward launch ran proj_out + residual too
-                return _Act(y[0], x.b, x.h, x.w, x.c)
-        out = rowchain.linear320(y, w_out, self.proj_out.bias, x.t, self, "proj_out", _cached)
+                return _Act(y[0], xr.b, x.h, x.w, x.c)
+        out = rowchain.linear320(y, w_out, self.proj_out.bias, xr.t, self, "proj_out", _cached)
         if out is None:
-            out = ops.linear(y, w_out, self.proj_out.bias, res=x.t)
-        return _Act(out, x.b, x.h, x.w, x.c)
+            out = ops.linear(y, w_out, self.proj_out.bias, res=xr.t)
+        return _Act(out, xr.b, x.h, x.w, x.c)
 
 
 class _Block(nn.Module):
@@ -646,6 +686,27 @@ class UNet2DConditionModel(nn.Module):
         tproj = ops.linear(ops.act(emb, ops.ACT_SILU), w, b)            # [B, sum(cout)]: all ResBlock time projections
         return emb, tproj
 
+    def _pair_prefix_ok(self, ca_kwargs, rows):
+        """the half-batch prefix exists for this model and call: the first down block has attention (else nothing in it reads the conditioning), its first
+        attn1 is a plain self-attention through our own processor whose output leaves through ``_finish``'s to_out GEMM with the block residual in its
+        epilogue (``pair_output`` hands that GEMM the pair tensor), no cross_attention_kwargs (attention-map capture, masks and process hooks are per batch
+        item) — and the half batch gets the kernel family the full batch gets: the row-chain launches (``rc_front``, ``rc_linear``) are chosen by row
+        count (``rowchain.MIN_ROWS_CHAIN`` = 32768), so a full batch of ``rows`` level-0 tokens at or above it whose half is below (4 to 7 images of 64 x 64)
+        would trade its fused front for four LDS-tiled launches: not measured, so not shared"""
+        blk = self.down_blocks[0]
+        if ca_kwargs or not blk.has_cross_attention or len(blk.resnets) == 0:
+            return False
+        tfm0 = blk.attentions[0]
+        if len(tfm0.transformer_blocks) == 0:
+            return False
+        a1 = tfm0.transformer_blocks[0].attn1
+        if type(a1.processor) is not AttnProcessor or a1.rescale_output_factor != 1.0 or a1.residual_connection:
+            return False
+        if getattr(a1, "group_norm", None) is not None or getattr(a1, "spatial_norm", None) is not None:
+            return False
+        chain = rowchain.ENABLED and self.config.block_out_channels[0] == 320
+        return not (chain and rows >= rowchain.MIN_ROWS_CHAIN > rows // 2)
+
     def _residual(self, act: _Act, extra):
         """ControlNet / adapter residual added to a token-major activation: an NCHW tensor (diffusers module) or a
         token-major ``_Act`` handed over by ``theatergen_amd.controlnet.ControlNetModel(token_major=True)``."""
@@ -678,8 +739,12 @@ class UNet2DConditionModel(nn.Module):
 
     def forward(self, sample, timestep, encoder_hidden_states, class_labels=None, timestep_cond=None, attention_mask=None,
                 cross_attention_kwargs=None, added_cond_kwargs=None, down_block_additional_residuals=None,
-                mid_block_additional_residual=None, encoder_attention_mask=None, return_dict=True, out_dtype=None, time_proj=None):
-        """``time_proj`` (optional, [B, sum(cout)] storage dtype): the fused ResBlock time projections of THIS timestep, precomputed by the caller with
+                mid_block_additional_residual=None, encoder_attention_mask=None, return_dict=True, out_dtype=None, time_proj=None, shared_pair=False):
+        """``shared_pair``: the caller vouches that ``sample[:B/2]`` and ``sample[B/2:]`` hold the same values and see the same time projection (the CFG batch
+        ``torch.cat([latents] * 2)`` of models/pipelines.py:411-414; ``DenoiseEngine`` owns such an input) — everything in front of the first reader of
+        ``encoder_hidden_states`` (conv_in, down_blocks[0].resnets[0], the first transformer's front and attn1) then runs on half the batch.  Not checked
+        (that would take a device sync): the default is False.  Odd B raises ValueError.
+        ``time_proj`` (optional, [B, sum(cout)] storage dtype): the fused ResBlock time projections of THIS timestep, precomputed by the caller with
         ``time_embed`` (``DenoiseEngine`` keeps one row per step of its schedule: the embedding depends on the timestep only) — the five launches of
         ``time_embed`` are skipped."""
         cfg = self.config
@@ -703,8 +768,11 @@ class UNet2DConditionModel(nn.Module):
         else:
             _, tproj = self.time_embed(timestep, B, added_cond_kwargs)
 
+        if shared_pair and B % 2:
+            raise ValueError(f"shared_pair needs an even batch (two equal halves), got {B}")
+        share = shared_pair and _CFG_SHARE and self._pair_prefix_ok(ca_kwargs, B * H * W)
         w_in = self._p.get("conv_in", [self.conv_in.weight], lambda: pack_conv3x3(self.conv_in.weight.detach()))
-        x = _Act(ops.conv_in(sample.contiguous(), w_in, self.conv_in.bias, cfg.block_out_channels[0], dt), B, H, W,
+        x = _Act(ops.conv_in(sample.contiguous(), w_in, self.conv_in.bias, cfg.block_out_channels[0], dt, pair=share), B, H, W,
                  cfg.block_out_channels[0])
 
         is_controlnet = mid_block_additional_residual is not None and down_block_additional_residuals is not None
@@ -719,11 +787,17 @@ class UNet2DConditionModel(nn.Module):
             cross_feat = feats.pop(0) if blk.has_cross_attention and feats else None
             last = len(blk.resnets) - 1
             for j, resnet in enumerate(blk.resnets):
-                x = resnet.run(x, None, tproj)
+                xh = None
+                if share and i == 0 and j == 0:
+                    # the pair's common prefix on rows [:B/2]; x (conv_in's output, the last up-block skip) already holds both halves
+                    hb = B // 2
+                    xh, x = resnet.run(_Act(x.t[:hb * x.hw], hb, x.h, x.w, x.c), None, tproj[:hb], pair=True, pair_src=x)
+                else:
+                    x = resnet.run(x, None, tproj)
                 if blk.has_cross_attention:
                     if track_keys:
                         ca_kwargs["attn_key"] = ["down", i, j]
-                    x = blk.attentions[j].run(x, enc, ca_kwargs)
+                    x = blk.attentions[j].run(x, enc, ca_kwargs) if xh is None else blk.attentions[j].run(xh, enc, ca_kwargs, pair_full=x)
                     if j == last and cross_feat is not None:
                         x = self._adapter_add(x, cross_feat)
                 res.append(x)

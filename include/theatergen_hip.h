@@ -224,6 +224,23 @@ typedef struct {
 } tg_attn_desc;
 
 int tg_attention(const tg_attn_desc* d, void* stream);
+/* The same descriptor for WIDE heads, head_dim 256 or 512, ONE softmax segment (csrc/tg_attention_wide.hip; the VAE mid block's single-head d = C attention):
+ *     O = softmax(s Q K0^T) V0
+ * Nothing [n_q, len0] exists in memory: scores are accumulated in fp32 from the stored q / k0, the softmax is online (running max and sum in fp32), P is
+ * rounded to the storage dtype where it enters the PV product (as tg_attention does), O is accumulated in fp32 and rounded once.  One launch covers
+ * batch x heads x query blocks of 128 rows (x 2 column halves at head_dim 512: each workgroup recomputes the scores over the full head dim and owns 256
+ * output columns; every output element is written by exactly one lane, no atomics, no workspace).  Layouts and pitches as tg_attention.  Any n_q >= 1:
+ * rows >= n_q of q are never read, rows >= n_q of out never written, nor columns >= heads * head_dim of either.  len0 is a multiple of 8; keys past it
+ * contribute exactly 0 to the max, the sum and PV (columns >= len0 of a vt0 row and rows >= len0 of k0 are never read).
+ * Validation is on the host, before any launch; a refused descriptor writes nothing:
+ *   TG_ERR_UNSUPPORTED  head_dim not in {256, 512}; len1 != 0, causal, mask or w1_dev set (tg_attention's second segment, masks and device scalar
+ *                       have no wide counterpart);
+ *   TG_ERR_ARG          null descriptor / pointers, bad dtype, empty problem, len0 % 8 != 0, scale <= 0, q_ld / k0_ld / vt0_ld not multiples of 8 or
+ *                       out_ld not a multiple of 4 (the 16-byte / 8-byte accesses of tg_attention); with batch > 1 the same for the batch strides
+ *                       (q_bs, k0_bs, vt0_bs multiples of 8, out_bs of 4: they move the same accesses).  q, k0, vt0 must be 16-byte aligned, out 8-byte.
+ *   TG_ERR_LAUNCH       the device refuses the kernel's dynamic LDS (96 KiB per workgroup at head_dim 512) or the launch.
+ * Additive to ABI 308: one new symbol, tg_attn_desc unchanged, TG_ABI_VERSION unchanged. */
+int tg_attention_wide(const tg_attn_desc* d, void* stream);
 
 /* Reverse pass of SELF-attention without materialised probabilities (round 5, ABI 306; csrc/tg_attention_bwd.hip), head_dim <= 64, n % 8 == 0:
  *     dQ = dS K,  dK = dS^T Q,  dV = P^T dO   with  P = softmax(scale Q K^T),  dS = scale P o (dO V^T - rowsum(P o dO V^T))

@@ -136,6 +136,7 @@ SIGNATURES = {
     "tg_gemm_workspace_bytes": (i64, [C.POINTER(GemmDesc)]),
     "tg_gemm_plan": (i32, [C.POINTER(GemmDesc), vp, vp, vp, vp]),
     "tg_attention": (i32, [C.POINTER(AttnDesc), vp]),
+    "tg_attention_wide": (i32, [C.POINTER(AttnDesc), vp]),
     "tg_attention_bwd": (i32, [C.POINTER(AttnBwdDesc), vp]),
     "tg_attention_bwd_cross": (i32, [C.POINTER(AttnBwdCrossDesc), vp]),
     "tg_attention_bwd_wide": (i32, [C.POINTER(AttnBwdDesc), vp]),

@@ -128,6 +128,9 @@ HOT_GATES = [
     ("attention_kernel<bf16,48,64,true,true,false,false>", 0, 128),
     ("attention_kernel<f16,48,64,true,true,false,false>", 0, 128),
     ("attention_kernel<", 0, 256),
+    # head dims 256 / 512 (tg_attention_wide.hip, template <T, D, DO>): one wave per SIMD, Q fragment D / 4 registers + O^T accumulator DO / 2.  Scratch 0 is what
+    # chose DO = 256 at d = 512 (<T,512,256>: 256 VGPRs + 208 AGPRs; the full-width <T,512,512> instance spilled 996 bytes inside the key loop)
+    ("attention_wide_kernel<", 0, 256),
     ("gemm_glds_kernel<", 0, 256),                                 # the LDS-DMA GEMM family: no scratch anywhere
     ("conv_halo_kernel<", 0, 256),
     # families that DO spill today (8-wave loader / compute kernels, 256-register budget): ceilings = the round-3 values, so a

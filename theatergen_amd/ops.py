@@ -519,6 +519,34 @@ def attention(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch,
     return out
 
 
+def attention_wide(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale, out, out_ld, out_bs):
+    """``tg_attention_wide``: one-segment flash attention for head dims 256 / 512 (the VAE mid block), the argument list of ``attention`` without
+    the second segment, mask, causal flag and device scalar.  Another head dim is an error (``attention`` takes multiples of 8 up to 160)."""
+    _need_cuda(q)
+    d = AttnDesc()
+    d.dtype = _dt(q)
+    d.batch, d.heads, d.head_dim, d.n_q = int(batch), int(heads), int(head_dim), int(n_q)
+    d.q, d.q_ld, d.q_bs = _ptr(q), int(q_ld), int(q_bs)
+    d.k0, d.k0_ld, d.k0_bs = _ptr(k0), int(k0_ld), int(k0_bs)
+    d.vt0, d.vt0_ld, d.vt0_bs = _ptr(vt0), int(vt0_ld), int(vt0_bs)
+    d.len0 = int(len0)
+    d.scale = float(scale)
+    d.out, d.out_ld, d.out_bs = _ptr(out), int(out_ld), int(out_bs)
+    if _gemm_profile is None:
+        _lib.check(_lib.lib().tg_attention_wide(C.byref(d), _stream()))
+        return out
+    # profiling mode (bench.py roofline leg), as ``attention``: algorithmic flops = QK^T + PV, no recomputed column half counted
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    _lib.check(_lib.lib().tg_attention_wide(C.byref(d), _stream()))
+    e1.record()
+    _gemm_profile.append(dict(kernel=f"attention_wide_kernel<d{int(head_dim)}>", splits=1,
+                              M=int(batch) * int(n_q), N=int(heads) * int(head_dim), K=int(len0),
+                              flops=4.0 * batch * heads * n_q * len0 * head_dim, events=(e0, e1), has_res=False,
+                              n_out=int(heads) * int(head_dim), attention=True, batch=int(batch)))
+    return out
+
+
 def attn_probs(q, q_ld, q_bs, k, k_ld, k_bs, batch, b0, heads, head_dim, n_q, length, scale, tokens=None):
     """fp32 [batch-b0, heads, n_q, n_tokens] softmax probabilities (save_attn_to_dict side channel)."""
     nt = length if tokens is None else int(tokens.numel())

@@ -14,7 +14,10 @@ UNet's kernels: GroupNorm(+SiLU), conv3x3 (LDS-halo kernel at widths <= 64, impl
 folded into the conv gather, 1x1 shortcut GEMMs with the residual in the epilogue.  The mid block's single-head d = 512
 attention (4096 tokens) is outside the fused flash kernel's register budget and runs once per image: fused Q|K|V^T
 projection GEMM -> scores GEMM -> ``tg_softmax_rows`` -> PV GEMM -> output projection with the residual fused.
+Opt-in (``TG_VAE_FLASH=1`` or ``flash=True``): one Q|K|V^T projection GEMM and ONE flash launch for the whole batch
+(``tg_attention_wide`` at C = 256 / 512, ``tg_attention`` at C <= 160), no [N, N] scores tensor.
 """
+import os
 from types import SimpleNamespace
 
 import torch
@@ -48,9 +51,10 @@ def tiny_vae_config():
 class VAEAttention(nn.Module):
     """diffusers ``Attention(C, heads=1, dim_head=C, bias=True, norm_num_groups=32, residual_connection=True)``"""
 
-    def __init__(self, channels, groups=32, eps=1e-6):
+    def __init__(self, channels, groups=32, eps=1e-6, flash=None):
         super().__init__()
         self.channels, self.groups, self.eps = channels, groups, eps
+        self.flash = flash                      # True / False, or None: the environment's TG_VAE_FLASH=1 decides (default off)
         self.group_norm = nn.GroupNorm(groups, channels, eps=eps)
         self.to_q = nn.Linear(channels, channels)
         self.to_k = nn.Linear(channels, channels)
@@ -58,10 +62,36 @@ class VAEAttention(nn.Module):
         self.to_out = nn.ModuleList([nn.Linear(channels, channels)])
         self._p = _Packed()
 
+    def flash_route(self):
+        """the flash route is selected AND there is a kernel for this channel count (other counts keep the materialised path)"""
+        on = self.flash if self.flash is not None else os.environ.get("TG_VAE_FLASH") == "1"
+        C = self.channels
+        return bool(on) and ((C <= 160 and C % 8 == 0) or C in (256, 512))
+
+    def _run_flash(self, x: _Act):
+        """GroupNorm -> one GEMM (Q | K rows + V^T, as ``attention_processor.qkv_weight`` / ``self_attention_from_qkv``) -> one flash launch for
+        the whole batch (scores stay fp32 until P) -> to_out with the residual fused"""
+        C, N, B = self.channels, x.hw, x.b
+        lins = [self.to_q, self.to_k, self.to_v]
+        ws = [l.weight for l in lins] + [l.bias for l in lins]
+        wqkv, bqkv = self._p.get("qkv", ws, lambda: (torch.cat([t.detach() for t in ws[:3]], 0).contiguous(),
+                                                     torch.cat([t.detach() for t in ws[3:]], 0).contiguous()))
+        y = ops.groupnorm(x.t, B, N, self.groups, self.eps, self.group_norm.weight, self.group_norm.bias, silu=False)
+        qk = torch.empty((B * N, 2 * C), dtype=y.dtype, device=y.device)
+        vt = torch.empty((B, C, N), dtype=y.dtype, device=y.device)
+        ops.gemm(y, wqkv, B * N, 3 * C, C, bias=bqkv, rows_per_batch=N, out=qk, n_split=2 * C, out_t=vt, ldt=N)
+        o = torch.empty((B * N, C), dtype=y.dtype, device=y.device)
+        attn = ops.attention if C <= 160 else ops.attention_wide
+        attn(qk, 2 * C, N * 2 * C, qk[:, C:], 2 * C, N * 2 * C, vt, N, C * N, N, B, 1, C, N, float(C) ** -0.5, o, C, N * C)
+        out = ops.linear(o, self.to_out[0].weight, self.to_out[0].bias, res=x.t)
+        return _Act(out, x.b, x.h, x.w, C)
+
     def run(self, x: _Act):
         C, N, B = self.channels, x.hw, x.b
         if N % 8 != 0:
             raise RuntimeError("VAE attention needs a token count that is a multiple of 8")
+        if self.flash_route():
+            return self._run_flash(x)
         ws = [self.to_k.weight, self.to_v.weight, self.to_k.bias, self.to_v.bias]
         wkv, bkv = self._p.get("kv", ws, lambda: (torch.cat([t.detach() for t in ws[:2]], 0).contiguous(),
                                                   torch.cat([t.detach() for t in ws[2:]], 0).contiguous()))
@@ -88,14 +118,14 @@ class _UpBlock(nn.Module):
 
 
 class Decoder(nn.Module):
-    def __init__(self, cfg):
+    def __init__(self, cfg, flash=None):
         super().__init__()
         boc = tuple(cfg.block_out_channels)
         g = cfg.norm_num_groups
         self.conv_in = nn.Conv2d(cfg.latent_channels, boc[-1], 3, padding=1)
         mid = nn.Module()
         mid.resnets = nn.ModuleList([ResnetBlock2D(boc[-1], boc[-1], None, g, 1e-6), ResnetBlock2D(boc[-1], boc[-1], None, g, 1e-6)])
-        mid.attentions = nn.ModuleList([VAEAttention(boc[-1], g, 1e-6)])
+        mid.attentions = nn.ModuleList([VAEAttention(boc[-1], g, 1e-6, flash)])
         self.mid_block = mid
         self.up_blocks = nn.ModuleList()
         rboc = tuple(reversed(boc))
@@ -138,7 +168,7 @@ class Encoder(nn.Module):
     ResnetBlock2D(temb=None, eps 1e-6) + a padding-0 downsample on all but the last), UNetMidBlock2D (1 head), GroupNorm ->
     SiLU -> conv_out to 2 * latent_channels."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, flash=None):
         super().__init__()
         boc = tuple(cfg.block_out_channels)
         g = cfg.norm_num_groups
@@ -155,7 +185,7 @@ class Encoder(nn.Module):
             prev = c
         mid = nn.Module()
         mid.resnets = nn.ModuleList([ResnetBlock2D(boc[-1], boc[-1], None, g, 1e-6), ResnetBlock2D(boc[-1], boc[-1], None, g, 1e-6)])
-        mid.attentions = nn.ModuleList([VAEAttention(boc[-1], g, 1e-6)])
+        mid.attentions = nn.ModuleList([VAEAttention(boc[-1], g, 1e-6, flash)])
         self.mid_block = mid
         self.conv_norm_out = nn.GroupNorm(g, boc[-1], eps=1e-6)
         self.conv_out = nn.Conv2d(boc[-1], 2 * cfg.latent_channels, 3, padding=1)
@@ -202,14 +232,15 @@ class DecoderOutput(SimpleNamespace):
 
 
 class AutoencoderKL(nn.Module):
-    def __init__(self, config=None, **kw):
+    def __init__(self, config=None, flash=None, **kw):
+        """``flash``: the mid blocks' attention route (``VAEAttention.flash``): True / False, or None = ``TG_VAE_FLASH=1`` decides (default off)"""
         super().__init__()
         self.config = config if config is not None else sd_vae_config(**kw)
         lc = self.config.latent_channels
-        self.encoder = Encoder(self.config)
+        self.encoder = Encoder(self.config, flash)
         self.quant_conv = nn.Conv2d(2 * lc, 2 * lc, 1)
         self.post_quant_conv = nn.Conv2d(lc, lc, 1)
-        self.decoder = Decoder(self.config)
+        self.decoder = Decoder(self.config, flash)
         self._p = _Packed()
         for p_ in self.parameters():
             p_.requires_grad_(False)
@@ -293,9 +324,9 @@ class AutoencoderKL(nn.Module):
         return DecoderOutput(sample=img)
 
     @classmethod
-    def from_state_dict(cls, config, state_dict, device="cuda", dtype=torch.bfloat16):
+    def from_state_dict(cls, config, state_dict, device="cuda", dtype=torch.bfloat16, flash=None):
         """a decoder-only state dict (no ``encoder.*`` keys) builds a decode-only module"""
-        m = cls(config)
+        m = cls(config, flash=flash)
         if not any(k.startswith("encoder.") for k in state_dict):
             del m.encoder, m.quant_conv
             m.encoder = m.quant_conv = None

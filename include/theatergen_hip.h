@@ -420,6 +420,25 @@ int tg_step_epilogue_sigma(const float* noise_pred, float* latents, int32_t n_im
                            int32_t mask_per_img, int32_t frozen_steps, float* history, void* model_in, int32_t model_in_dtype,
                            void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Step epilogue of the DPM-Solver++ multistep scheduler (data prediction, midpoint, orders 1 and 2; additive to ABI 308):
+ * CFG combine m = u + g (c - u), then with the row r = coef[s] (DEVICE fp32 [n_steps][8] = {cx, ce, A, B, C, 0, 0, 0}, s = *step_idx)
+ *   x0 = cx x + ce m                 (epsilon: cx = 1 / alpha_s, ce = -sigma_s / alpha_s; v: cx = alpha_s, ce = -sigma_s)
+ *   x' = A x + B x0 + C x0_prev      (A = sigma_t / sigma_s, B = E + E / (2 r0), C = -E / (2 r0), E = -alpha_t expm1(-h);
+ *                                     first-order rows: B = E and C exactly 0.0f)
+ * x0_prev: DEVICE fp32 [n_img * chw], required, a buffer of its own.  Each element is READ only when C != 0 (the row is the same
+ * for all threads; an unwritten buffer may hold NaN and 0 * NaN is NaN) and then OVERWRITTEN with this step's x0 by the same
+ * thread.  x0 is the model's prediction: the frozen-mask blend that follows changes x' only.  Then, as tg_step_epilogue: the
+ * blend with frozen row s+1 while s < frozen_steps, the history row s+1, the next UNet input model_in = cat([x'] * 2) rounded
+ * once to model_in_dtype (TG_BF16, TG_F16 or 2 = fp32; no input scaling, init_noise_sigma = 1).  step_idx is read by the
+ * epilogue and, when `advance`, incremented by a launch of its own after it (as tg_step_epilogue_sigma): no thread reads a
+ * moved counter.  The schedule math (lambda, h, r0) is the host's, in fp64, rounded to fp32 once: the device only applies rows.
+ */
+int tg_step_epilogue_dpm(const float* noise_pred, float* latents, float* x0_prev, int32_t n_img, int32_t chw, int32_t hw,
+                         int32_t has_cfg, float guidance_scale, const float* coef, int32_t* step_idx, int32_t advance,
+                         const float* frozen, const float* frozen_mask, int32_t mask_per_img, int32_t frozen_steps,
+                         float* history, void* model_in, int32_t model_in_dtype, void* stream);
+
 /* T2I-Adapter pieces (diffusers T2IAdapter "full_adapter_xl"), storage dtype in / out:
  * tg_pixel_unshuffle: NCHW [batch, C, h, w] -> token-major [batch * (h/f) * (w/f), C f^2], channel c f^2 + i f + j from pixel
  *                     (f y + i, f x + j) (F.pixel_unshuffle); pure data movement.

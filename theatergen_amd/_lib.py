@@ -167,6 +167,7 @@ SIGNATURES = {
     "tg_timestep_embedding": (i32, [i32, vp, vp, i32, i32, i32, i32, f32, vp, i64, vp]),
     "tg_step_epilogue": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, vp]),
     "tg_step_epilogue_sigma": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp]),
+    "tg_step_epilogue_dpm": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp]),
     "tg_pixel_unshuffle": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp]),
     "tg_relu": (i32, [i32, vp, i64, vp, vp]),
     "tg_avgpool2x2": (i32, [i32, vp, i32, i32, i32, i32, vp, vp]),

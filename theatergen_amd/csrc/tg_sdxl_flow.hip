@@ -1,5 +1,6 @@
 // The SDXL flow around the UNet: the sigma-parameterised step epilogue (CFG + Euler / Euler-ancestral update + frozen-mask
-// blend + history row + next scaled model input, one launch per step) and the T2I-Adapter's data-movement / pointwise pieces
+// blend + history row + next scaled model input, one launch per step), its DPM-Solver++ multistep sibling (tg_step_epilogue_dpm:
+// one extra fp32 state tensor, the previous data prediction) and the T2I-Adapter's data-movement / pointwise pieces
 // (pixel-unshuffle into token-major, ReLU, 2 x 2 ceil-mode average pool, scale-and-repeat of the conditioning features).
 // Everything here is HBM-bound and runs once per step or once per image; no hot GEMM / conv epilogue is touched.
 #include "tg_common.h"
@@ -74,6 +75,67 @@ __global__ __launch_bounds__(256) void step_epilogue_sigma_kernel(SigmaStepParam
 }
 
 __global__ void sigma_step_advance_kernel(int* step_idx) { *step_idx += 1; }
+
+struct DpmStepParams {
+  const float* noise_pred;
+  float* latents;
+  float* x0_prev;             // [n_img * chw] fp32: the previous step's data prediction, replaced by this step's
+  int n_img, chw, hw;
+  int has_cfg;
+  float g;
+  const float* coef;          // [n_steps][8]: cx, ce, A, B, C, 0, 0, 0
+  int* step_idx;
+  const float* frozen;
+  const float* frozen_mask;
+  int mask_per_img;
+  int frozen_steps;
+  float* history;
+  void* model_in;
+  int model_in_dtype;
+};
+
+// DPM-Solver++ multistep (data prediction, midpoint 2M): x0 = cx x + ce m, x' = A x + B x0 + C x0_prev with the row of this
+// step.  C == 0 marks a first-order row: the state is then NOT read (0 * NaN of a never-written buffer would be NaN); the row is
+// the same for every thread, so the branch is wave-uniform.  Each element of x0_prev is read and rewritten by one thread only.
+__global__ __launch_bounds__(256) void step_epilogue_dpm_kernel(DpmStepParams p) {
+  const int step = *p.step_idx;
+  const float* row = p.coef + (long)step * 8;
+  const float cx = row[0], ce = row[1], ca = row[2], cb = row[3], cc = row[4];
+  const bool second = cc != 0.f;
+  const long total = (long)p.n_img * p.chw;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const float u = p.noise_pred[i];
+    float m = u;
+    if (p.has_cfg) { const float c = p.noise_pred[total + i]; m = u + p.g * (c - u); }
+    const float x = p.latents[i];
+    const float x0 = cx * x + ce * m;
+    float nx = ca * x + cb * x0;
+    if (second) nx += cc * p.x0_prev[i];
+    p.x0_prev[i] = x0;                     // the model's prediction, not the blended latents (host loop: scheduler.step, then the blend)
+    if (p.frozen && step < p.frozen_steps) {
+      const long img = i / p.chw;
+      const long pix = (i - img * p.chw) % p.hw;
+      const float mk = p.frozen_mask[(p.mask_per_img ? img * p.hw : 0) + pix];
+      const float f = p.frozen[(long)(step + 1) * total + i];
+      nx = f * mk + nx * (1.f - mk);
+    }
+    p.latents[i] = nx;
+    if (p.history) p.history[(long)(step + 1) * total + i] = nx;
+    if (p.model_in) {
+      // next UNet input = cat([latents] * 2) in the model dtype (scale_model_input is the identity: init_noise_sigma = 1)
+      if (p.model_in_dtype == TG_BF16) {
+        reinterpret_cast<bf16_t*>(p.model_in)[i] = (bf16_t)nx;
+        reinterpret_cast<bf16_t*>(p.model_in)[total + i] = (bf16_t)nx;
+      } else if (p.model_in_dtype == TG_F16) {
+        reinterpret_cast<f16_t*>(p.model_in)[i] = (f16_t)nx;
+        reinterpret_cast<f16_t*>(p.model_in)[total + i] = (f16_t)nx;
+      } else {
+        reinterpret_cast<float*>(p.model_in)[i] = nx;
+        reinterpret_cast<float*>(p.model_in)[total + i] = nx;
+      }
+    }
+  }
+}
 
 // out[((b * oh + y) * ow + x) * (C r^2) + c r^2 + i r + j] = in[b, c, r y + i, r x + j]   (F.pixel_unshuffle, token-major)
 template <typename T>
@@ -150,6 +212,30 @@ extern "C" int tg_step_epilogue_sigma(const float* noise_pred, float* latents, i
   hipLaunchKernelGGL(step_epilogue_sigma_kernel, dim3(blocks_for((long)n_img * chw)), dim3(256), 0, st, p);
   TG_LAUNCH_CHECK();
   if (advance) {
+    hipLaunchKernelGGL(sigma_step_advance_kernel, dim3(1), dim3(1), 0, st, step_idx);
+    TG_LAUNCH_CHECK();
+  }
+  return TG_OK;
+}
+
+extern "C" int tg_step_epilogue_dpm(const float* noise_pred, float* latents, float* x0_prev, int32_t n_img, int32_t chw, int32_t hw,
+                                    int32_t has_cfg, float guidance_scale, const float* coef, int32_t* step_idx, int32_t advance,
+                                    const float* frozen, const float* frozen_mask, int32_t mask_per_img, int32_t frozen_steps,
+                                    float* history, void* model_in, int32_t model_in_dtype, void* stream) {
+  TG_CHECK(noise_pred && latents && x0_prev && coef && step_idx && n_img > 0 && chw > 0 && hw > 0 && chw % hw == 0, TG_ERR_ARG,
+           "tg_step_epilogue_dpm: bad args");
+  TG_CHECK(x0_prev != latents && (const float*)x0_prev != noise_pred, TG_ERR_ARG,
+           "tg_step_epilogue_dpm: x0_prev must be a buffer of its own");
+  TG_CHECK(!model_in || model_in_dtype == TG_BF16 || model_in_dtype == TG_F16 || model_in_dtype == 2, TG_ERR_ARG,
+           "tg_step_epilogue_dpm: model_in dtype must be TG_BF16, TG_F16 or 2 (fp32)");
+  TG_CHECK(!frozen || frozen_mask, TG_ERR_ARG, "tg_step_epilogue_dpm: frozen latents need a mask");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  DpmStepParams p{noise_pred, latents, x0_prev, n_img, chw, hw, has_cfg, guidance_scale, coef, step_idx, frozen,
+                  frozen_mask, mask_per_img, frozen_steps, history, model_in, model_in_dtype};
+  hipLaunchKernelGGL(step_epilogue_dpm_kernel, dim3(blocks_for((long)n_img * chw)), dim3(256), 0, st, p);
+  TG_LAUNCH_CHECK();
+  if (advance) {
+    // a launch of its own, ordered after the epilogue on the stream: no thread of the epilogue can read a moved counter
     hipLaunchKernelGGL(sigma_step_advance_kernel, dim3(1), dim3(1), 0, st, step_idx);
     TG_LAUNCH_CHECK();
   }

@@ -856,6 +856,25 @@ def step_epilogue_sigma(noise_pred, latents, guidance_scale, coef, step_idx, *, 
                                                  _stream()))
 
 
+def step_epilogue_dpm(noise_pred, latents, x0_prev, guidance_scale, coef, step_idx, *, has_cfg=True, advance=True, frozen=None,
+                      frozen_mask=None, frozen_steps=0, history=None, model_in=None):
+    """DPM-Solver++ multistep step (``tg_step_epilogue_dpm``): ``coef`` = ``DPMSolverMultistepScheduler.coef_table`` on the device
+    (fp32 [n_steps, 8]), ``x0_prev`` = the fp32 state tensor shaped like ``latents`` (read when the row's C != 0, then overwritten)"""
+    n_img = latents.shape[0]
+    chw = latents[0].numel()
+    hw = latents.shape[-1] * latents.shape[-2]
+    if x0_prev is None or x0_prev.dtype != torch.float32 or x0_prev.numel() != latents.numel() or not x0_prev.is_contiguous():
+        raise ValueError("step_epilogue_dpm: x0_prev must be a contiguous fp32 tensor with the latents' element count")
+    if coef.dtype != torch.float32 or coef.dim() != 2 or coef.shape[1] != 8 or not coef.is_contiguous():
+        raise ValueError("step_epilogue_dpm: coef must be a contiguous fp32 [n_steps, 8] table")
+    mask_per_img = 1 if (frozen_mask is not None and frozen_mask.numel() == n_img * hw and n_img > 1) else 0
+    mi_dt = -1 if model_in is None else _SRC[model_in.dtype]
+    _lib.check(_lib.lib().tg_step_epilogue_dpm(_ptr(noise_pred), _ptr(latents), _ptr(x0_prev), n_img, chw, hw, 1 if has_cfg else 0,
+                                               float(guidance_scale), _ptr(coef), _ptr(step_idx), 1 if advance else 0, _ptr(frozen),
+                                               _ptr(frozen_mask), mask_per_img, int(frozen_steps), _ptr(history), _ptr(model_in), mi_dt,
+                                               _stream()))
+
+
 def pixel_unshuffle(x, factor):
     """NCHW [B, C, h, w] (bf16 / fp16) -> token-major [B * (h/f) * (w/f), C f^2] (``F.pixel_unshuffle`` then NHWC)"""
     _need_cuda(x)

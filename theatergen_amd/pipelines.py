@@ -17,7 +17,7 @@ import torch
 
 from . import ops
 from .attention_processor import register_replay_stream, tensor_version, unregister_replay_stream
-from .scheduler import DDIMScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler
 from .unet import DeviceSchedule
 
 
@@ -60,7 +60,8 @@ class DenoiseEngine:
                  enc_len=81, use_graph=True, controlnet=None, controlnet_enc_len=77, timesteps=None):
         """``timesteps`` (optional): a SUBSET of ``scheduler.set_timesteps(num_inference_steps)`` to walk instead of all of them — the reference's fast
         schedule (``utils/schedule.py:4-8`` applied at ``models/pipelines.py:383-384``); as in the reference the DDIM update of a kept step still jumps by
-        the full schedule's stride (``prev_t = t - 1000 // num_inference_steps``)."""
+        the full schedule's stride (``prev_t = t - 1000 // num_inference_steps``).  A ``DPMSolverMultistepScheduler`` gets the subset as the walked list:
+        each step goes to the next KEPT timestep and r0 follows the real lambda spacing."""
         self.unet = unet
         self.ws_slot = next(_engine_ids)      # private kernel scratch: engines may replay concurrently on different streams
         # stage 2 (reference pipelines.py:759-818): every step the ControlNet runs on the same model input with the TEXT
@@ -75,11 +76,18 @@ class DenoiseEngine:
         dev, dt, cfg = unet.device, unet.dtype, unet.config
         self.dev, self.dt = dev, dt
         C = cfg.in_channels
-        self.scheduler.set_timesteps(num_inference_steps)
-        # DDIM: the reference's own update; Euler / Euler ancestral (the SDXL flow): sigma-parameterised update, tg_step_epilogue_sigma
+        # DDIM: the reference's own update; Euler / Euler ancestral (the SDXL flow): sigma-parameterised update, tg_step_epilogue_sigma;
+        # DPM-Solver++ multistep (opt-in, models/models.py:36-37): tg_step_epilogue_dpm with one extra state tensor
         self.kind = ("euler_a" if isinstance(self.scheduler, EulerAncestralDiscreteScheduler) else
-                     "euler" if isinstance(self.scheduler, EulerDiscreteScheduler) else "ddim")
-        tdt = torch.int64 if self.kind == "ddim" else torch.float32
+                     "euler" if isinstance(self.scheduler, EulerDiscreteScheduler) else
+                     "dpm" if isinstance(self.scheduler, DPMSolverMultistepScheduler) else
+                     "ddim" if isinstance(self.scheduler, DDIMScheduler) else None)
+        if self.kind is None:
+            raise TypeError(f"DenoiseEngine: unsupported scheduler {type(self.scheduler).__name__}; the step epilogues exist for theatergen_amd.scheduler."
+                            "DDIMScheduler, EulerDiscreteScheduler, EulerAncestralDiscreteScheduler and DPMSolverMultistepScheduler")
+        self.sigma_kind = self.kind in ("euler", "euler_a")
+        self.scheduler.set_timesteps(num_inference_steps)
+        tdt = torch.float32 if self.sigma_kind else torch.int64
         self.timesteps = self.scheduler.timesteps.clone() if timesteps is None else torch.as_tensor(timesteps, dtype=tdt).clone()
         num_inference_steps = self.steps = int(self.timesteps.numel())
         self.t_table = self.timesteps.to(device=dev, dtype=torch.float32)
@@ -107,7 +115,11 @@ class DenoiseEngine:
         self.adapter_feats = None      # T2I-Adapter features: static CFG-duplicated token-major buffers (set_adapter)
         self.step_noise = None         # Euler ancestral: the per-step noise table (set_step_noise)
         self._noise_set = False
-        if self.kind != "ddim":
+        self.x0_prev = None
+        if self.kind == "dpm":
+            # the multistep state: allocated once (a captured graph holds its address); _reset leaves it alone, row 0 never reads it
+            self.x0_prev = torch.zeros_like(self.latents)
+        if self.sigma_kind:
             # scale_model_input of step 0 (the epilogue writes the later ones): x / sqrt(sigma_0^2 + 1)
             self.in_div0 = float(self.scheduler.model_input_divisor(self.scheduler.index_for_timestep(self.timesteps[0], self.timesteps)))
         if self.kind == "euler_a":
@@ -241,7 +253,11 @@ class DenoiseEngine:
         noise_pred = self.unet(self.model_in, self.sched, self.enc, added_cond_kwargs=self.added, return_dict=False,
                                out_dtype=torch.float32, down_block_additional_residuals=down,
                                mid_block_additional_residual=mid, time_proj=tp, shared_pair=self.added is None)[0]
-        if self.kind != "ddim":
+        if self.kind == "dpm":
+            ops.step_epilogue_dpm(noise_pred, self.latents, self.x0_prev, self.g, self.coef, self.step_idx, advance=True, frozen=self.frozen,
+                                  frozen_mask=self.frozen_mask, frozen_steps=self.frozen_steps, history=self.history, model_in=self.model_in)
+            return
+        if self.sigma_kind:
             ops.step_epilogue_sigma(noise_pred, self.latents, self.g, self.coef, self.step_idx, advance=True, noise=self.step_noise,
                                     frozen=self.frozen, frozen_mask=self.frozen_mask, frozen_steps=self.frozen_steps, history=self.history,
                                     model_in=self.model_in)
@@ -261,7 +277,7 @@ class DenoiseEngine:
     def _reset(self, latents):
         self.latents.copy_(latents.to(device=self.dev, dtype=torch.float32))
         self.history[0].copy_(self.latents)
-        if self.kind != "ddim":
+        if self.sigma_kind:
             x0 = self.latents / self.in_div0                      # scale_model_input of step 0, then the `.half()`
             self.model_in[:self.n_img].copy_(x0)
             self.model_in[self.n_img:].copy_(x0)
@@ -700,6 +716,39 @@ def final_image_generation(basever, processor, controlnetpipe, tpipe, overall_pr
     image = vae.decode(1 / 0.18215 * latents).sample
     image = (image.float() / 2 + 0.5).clamp(0, 1).detach().cpu().permute(0, 2, 3, 1).numpy()
     return latents, (image * 255).round().astype("uint8")
+
+
+@torch.no_grad()
+def decode(vae, latents):
+    """reference ``models/pipelines.py:163-173``: ``vae.decode(latents / 0.18215)`` -> ``(image / 2 + 0.5).clamp(0, 1)`` -> uint8 ``[n, H, W, 3]`` on the host"""
+    image = vae.decode(1 / 0.18215 * latents).sample
+    image = (image.float() / 2 + 0.5).clamp(0, 1).detach().cpu().permute(0, 2, 3, 1).numpy()
+    return (image * 255).round().astype("uint8")
+
+
+@torch.no_grad()
+def generate(adapter, model_dict, latents, input_embeddings, num_inference_steps, guidance_scale=7.5, no_set_timesteps=False, scheduler_key='scheduler'):
+    """reference ``models/pipelines.py:493-521``: the plain CFG loop over WHATEVER scheduler ``adapter.pipe.scheduler`` is (DDIM, DPM-Solver++ multistep,
+    Euler), then ``decode``; returns ``(latents, images uint8 [n, H, W, 3])``.  ``input_embeddings`` = ``(text_embeddings [2n, L, D] negatives first,
+    uncond, cond)``; only the first is read, as there.  On the engine: ``len(timesteps)`` replays of one captured step, no per-step host work.
+    ``no_set_timesteps=True`` walks the scheduler's CURRENT ``timesteps`` (a caller's own grid) and leaves them in place; their number must be
+    ``num_inference_steps`` (``ValueError``), since the engine's tables are built for that count.  ``scheduler_key`` is accepted and unused, as there."""
+    unet = _own_unet(adapter, "generate")
+    scheduler = adapter.pipe.scheduler
+    text_embeddings = input_embeddings[0]
+    timesteps = None
+    if no_set_timesteps:
+        timesteps = scheduler.timesteps.clone()
+        if int(timesteps.numel()) != int(num_inference_steps):
+            raise ValueError(f"generate(no_set_timesteps=True): the scheduler holds {int(timesteps.numel())} timesteps, num_inference_steps is {num_inference_steps}")
+    h8, w8 = latents.shape[-2], latents.shape[-1]
+    eng = _engine_of(adapter, n_img=latents.shape[0], height=8 * h8, width=8 * w8, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                     enc_len=text_embeddings.shape[1], timesteps=timesteps)
+    if timesteps is not None and not torch.equal(scheduler.timesteps, timesteps):
+        scheduler.timesteps = timesteps                              # building the engine's tables called set_timesteps: the caller's grid stays
+    eng.set_conditioning(text_embeddings.to(eng.dev, eng.dt))
+    out = eng.run(latents)[-1].to(latents.dtype, copy=True)          # a copy: the history row is the engine's buffer, the next run rewrites it
+    return out, decode(adapter.pipe.vae, out.to(unet.dtype))
 
 
 def latent_backward_guidance(*args, **kwargs):

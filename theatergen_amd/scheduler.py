@@ -6,6 +6,9 @@ GPU in ``tg_step_epilogue`` (CFG + DDIM + frozen-mask blend fused), fed by ``coe
 
 diffusers==0.21.4 semantics (not under /root/reference -> parity unpinned, see oracle/ddim.py): betas =
 linspace(sqrt(b0), sqrt(b1), T, fp32)**2, "leading" timestep spacing + steps_offset, eta = 0, no clipping.
+
+Also here, with the same call surface: the Euler / Euler-ancestral pair of the SDXL flow (``tg_step_epilogue_sigma``) and the opt-in
+DPM-Solver++ multistep sampler (``DPMSolverMultistepScheduler``, ``tg_step_epilogue_dpm``).
 """
 from types import SimpleNamespace
 
@@ -266,3 +269,187 @@ class EulerDiscreteScheduler(_SigmaScheduler):
 class EulerAncestralDiscreteScheduler(_SigmaScheduler):
     """``x' = x + eps (sigma_down - sigma_i) + sigma_up noise_i``: stage 2 of the SDXL flow (the T2I-Adapter pipeline's scheduler)"""
     ancestral = True
+
+
+class DPMSolverMultistepScheduler:
+    """DPM-Solver++ multistep, data prediction, midpoint second-order update ("2M"): the scheduler the reference's loader offers as
+    ``load_sd(use_dpm_multistep_scheduler=True)`` (``models/models.py:16, 36-37``).  A DIFFERENT sampler from the reference's default DDIM chain: one
+    extra state tensor (the previous step's data prediction), no extra UNet call; typically walked with 20-25 steps.
+
+    Schedule (all host math in fp64 on the fp32 ``alphas_cumprod`` DDIMScheduler has, rounded to fp32 once in ``coef_table``): a = alphas_cumprod,
+    alpha_t = sqrt(a_t), sigma_t = sqrt(1 - a_t), lambda_t = ln alpha_t - ln sigma_t.  The walked list is s_0 > s_1 > ... > s_{n-1}; step i goes from
+    s = s_i to t = s_{i+1}, the last one to t = 0 (a_0, not 1).  Data prediction: epsilon x0 = (x - sigma_s m) / alpha_s, v x0 = alpha_s x - sigma_s m.
+    With h = lambda_t - lambda_s and E = -alpha_t expm1(-h):
+        order 1:  x' = (sigma_t / sigma_s) x + E x0
+        order 2:  x' = (sigma_t / sigma_s) x + E x0 + E / (2 r0) (x0 - x0_prev),   r0 = (lambda_s - lambda_{s_{i-1}}) / h
+    Step 0 is first order; so is the last step when ``lower_order_final`` and n < 15; every other step has order ``solver_order``.
+
+    The update itself runs on the GPU (``tg_step_epilogue_dpm``) from one ``coef_table`` row per step.  diffusers is not a dependency: this is the
+    0.21.4 ``dpmsolver++`` / ``midpoint`` scheme restated; everything else that class offers is refused by name."""
+    order = 1                                  # UNet evaluations per step (the diffusers attribute): a multistep solver needs one
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", trained_betas=None, solver_order=2,
+                 prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0, algorithm_type="dpmsolver++",
+                 solver_type="midpoint", lower_order_final=True, use_karras_sigmas=False, lambda_min_clipped=-float("inf"), variance_type=None,
+                 timestep_spacing="linspace", steps_offset=0):
+        name = type(self).__name__
+        if trained_betas is not None:
+            raise NotImplementedError(f"{name}: trained_betas are not supported")
+        if algorithm_type != "dpmsolver++":
+            raise NotImplementedError(f"{name}: algorithm_type {algorithm_type!r} is not supported (dpmsolver++ only)")
+        if solver_type != "midpoint":
+            raise NotImplementedError(f"{name}: solver_type {solver_type!r} is not supported (midpoint only)")
+        if thresholding:
+            raise NotImplementedError(f"{name}: thresholding is not supported")
+        if use_karras_sigmas:
+            raise NotImplementedError(f"{name}: use_karras_sigmas is not supported")
+        if lambda_min_clipped != -float("inf"):
+            raise NotImplementedError(f"{name}: lambda_min_clipped other than -inf is not supported")
+        if variance_type is not None:
+            raise NotImplementedError(f"{name}: variance_type {variance_type!r} is not supported (the model output carries no variance)")
+        if solver_order not in (1, 2):
+            raise NotImplementedError(f"{name}: solver_order {solver_order!r} is not supported (1 or 2)")
+        if prediction_type not in ("epsilon", "v_prediction"):
+            raise NotImplementedError(f"{name}: prediction_type {prediction_type!r} is not supported (epsilon or v_prediction)")
+        if timestep_spacing not in ("linspace", "trailing"):
+            raise NotImplementedError(f"{name}: timestep_spacing {timestep_spacing!r} is not supported (linspace or trailing; pass any other grid, "
+                                      "DDIM's 'leading' one included, as set_timesteps(timesteps=...))")
+        if beta_schedule == "scaled_linear":
+            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        elif beta_schedule == "linear":
+            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        else:
+            raise ValueError(f"unknown beta_schedule {beta_schedule}")
+        self.betas = betas
+        self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
+        self.init_noise_sigma = 1.0
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+                                      trained_betas=None, solver_order=solver_order, prediction_type=prediction_type, thresholding=False,
+                                      dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value,
+                                      algorithm_type=algorithm_type, solver_type=solver_type, lower_order_final=lower_order_final,
+                                      use_karras_sigmas=False, lambda_min_clipped=-float("inf"), variance_type=None,
+                                      timestep_spacing=timestep_spacing, steps_offset=steps_offset)
+        self.num_inference_steps = None
+        self.timesteps = torch.from_numpy(np.arange(1, num_train_timesteps)[::-1].copy().astype(np.int64))
+        self._clear_state()
+
+    _CONFIG_KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "trained_betas", "prediction_type")
+    _OWN_KEYS = ("solver_order", "thresholding", "dynamic_thresholding_ratio", "sample_max_value", "algorithm_type", "solver_type", "lower_order_final",
+                 "use_karras_sigmas", "lambda_min_clipped", "variance_type", "timestep_spacing", "steps_offset")
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        """``DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)`` (the idiom of reference ``models/models.py:48``): betas, prediction type and
+        ``num_train_timesteps`` of any scheduler's config (a namespace or a dict).  The solver's own arguments (spacing included) are read only from a
+        config that is this class's (one that carries ``solver_order``): a DDIM config's "leading" spacing describes DDIM's grid, not this one's."""
+        get = config.get if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
+        miss = object()
+        keys = cls._CONFIG_KEYS + (cls._OWN_KEYS if get("solver_order", miss) is not miss else ())
+        kw = {k: get(k, miss) for k in keys}
+        kw = {k: v for k, v in kw.items() if v is not miss}
+        kw.update(overrides)
+        return cls(**kw)
+
+    def _clear_state(self):
+        self._x0_prev = None        # step(): the previous data prediction, fp32 on the device
+        self._taken = 0             # step(): updates made since set_timesteps
+        self._last_index = None
+        self._dev_tables = {}
+
+    def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None):
+        T = self.config.num_train_timesteps
+        if (num_inference_steps is None) == (timesteps is None):
+            raise ValueError("set_timesteps: pass exactly one of num_inference_steps and timesteps")
+        if timesteps is not None:
+            ts = np.asarray(torch.as_tensor(timesteps).cpu().numpy() if torch.is_tensor(timesteps) else timesteps)
+            if ts.ndim != 1 or ts.size == 0 or not np.all(ts == np.round(ts)):
+                raise ValueError("set_timesteps: timesteps must be a non-empty list of integers")
+            ts = ts.astype(np.int64)
+        else:
+            n = int(num_inference_steps)
+            if n < 1 or n > T - 1:
+                raise ValueError("num_inference_steps must be in [1, num_train_timesteps - 1]")
+            if self.config.timestep_spacing == "linspace":
+                ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+            else:
+                ts = (np.arange(T, 0, -T / n).round() - 1).astype(np.int64)
+        if ts.min() < 1 or ts.max() > T - 1 or np.any(np.diff(ts) >= 0):
+            raise ValueError(f"set_timesteps: timesteps must be strictly descending integers in [1, {T - 1}]")
+        self.num_inference_steps = int(ts.size)
+        self.timesteps = torch.from_numpy(ts)
+        self._clear_state()
+        return self.timesteps
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def _order_of(self, i, n):
+        if i == 0 or (i == n - 1 and self.config.lower_order_final and n < 15):
+            return 1
+        return self.config.solver_order
+
+    def _rows64(self, ts, orders=None):
+        """numpy fp64 [n, 8] rows (cx, ce, A, B, C, 0, 0, 0) of the walked list ``ts``"""
+        a = self.alphas_cumprod.to(torch.float64).numpy()
+        n = len(ts)
+        if n == 0 or min(ts) < 0 or max(ts) >= len(a) or any(ts[i + 1] >= ts[i] for i in range(n - 1)):
+            raise ValueError("coef_table: timesteps must be strictly descending integers of the training schedule")
+        alpha, sigma = np.sqrt(a), np.sqrt(1.0 - a)
+        lam = np.log(alpha) - np.log(sigma)
+        rows = np.zeros((n, 8), dtype=np.float64)
+        for i in range(n):
+            s, t = ts[i], (ts[i + 1] if i + 1 < n else 0)
+            h = lam[t] - lam[s]
+            e = -alpha[t] * np.expm1(-h)
+            if self.config.prediction_type == "epsilon":
+                rows[i, 0], rows[i, 1] = 1.0 / alpha[s], -sigma[s] / alpha[s]
+            else:
+                rows[i, 0], rows[i, 1] = alpha[s], -sigma[s]
+            rows[i, 2], rows[i, 3] = sigma[t] / sigma[s], e
+            if (self._order_of(i, n) if orders is None else orders[i]) == 2:
+                r0 = (lam[s] - lam[ts[i - 1]]) / h
+                rows[i, 3], rows[i, 4] = e + e / (2.0 * r0), -e / (2.0 * r0)
+        return rows
+
+    def coef_table(self, timesteps=None, dtype=torch.float32):
+        """[n_steps, 8] rows ``(cx, ce, A, B, C, 0, 0, 0)`` for the device epilogue: x0 = cx x + ce m, x' = A x + B x0 + C x0_prev; C is exactly 0 on
+        first-order rows.  ``timesteps`` (default ``self.timesteps``) is the list actually WALKED: a fast schedule passes its subset, so t of step i is the
+        next kept timestep, r0 follows the real lambda spacing and the order rules count the walked steps.  fp64 math; ``dtype=torch.float64`` keeps it."""
+        ts = [int(t) for t in (self.timesteps if timesteps is None else torch.as_tensor(timesteps)).tolist()]
+        return torch.from_numpy(self._rows64(ts)).to(dtype).contiguous()
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, **kw):
+        """Drop-in ``scheduler.step`` on the GPU (``tg_step_epilogue_dpm`` without CFG or mask).  The multistep state lives here: the previous data
+        prediction and the number of updates made, both cleared by ``set_timesteps``.  ``timestep`` is looked up in ``self.timesteps``; the steps must be
+        walked in order, and the first call after ``set_timesteps`` is a first-order update wherever in the list it starts."""
+        if kw:
+            raise NotImplementedError(f"{type(self).__name__}.step: unsupported arguments {sorted(kw)}")
+        dev = sample.device
+        hit = (self.timesteps == int(timestep)).nonzero()
+        if hit.numel() != 1:
+            raise ValueError(f"{type(self).__name__}.step: timestep {int(timestep)} is not in the schedule (call set_timesteps first)")
+        i = int(hit[0, 0])
+        if self._taken and i != self._last_index + 1:
+            raise ValueError(f"{type(self).__name__}.step: the multistep update needs the steps in order (step {self._last_index} was followed by {i}); "
+                             "set_timesteps(...) starts a new chain")
+        if dev not in self._dev_tables:
+            ts = [int(t) for t in self.timesteps.tolist()]
+            first = torch.from_numpy(self._rows64(ts, orders=[1] * len(ts))).to(dev, torch.float32).contiguous()
+            self._dev_tables[dev] = (self.coef_table().to(dev), first, torch.arange(len(ts), dtype=torch.int32, device=dev))
+        table, first, index = self._dev_tables[dev]
+        if self._x0_prev is None or self._x0_prev.shape != sample.shape or self._x0_prev.device != dev:
+            if self._taken:
+                raise ValueError(f"{type(self).__name__}.step: the sample changed shape or device inside a chain")
+            self._x0_prev = torch.empty(sample.shape, dtype=torch.float32, device=dev)
+        out = sample.detach().to(torch.float32).clone(memory_format=torch.contiguous_format)
+        ops.step_epilogue_dpm(model_output.detach().to(torch.float32).contiguous(), out, self._x0_prev, 0.0, table if self._taken else first,
+                              index[i:i + 1], has_cfg=False, advance=False)
+        self._taken += 1
+        self._last_index = i
+        out = out.to(sample.dtype)
+        if not return_dict:
+            return (out,)
+        return SimpleNamespace(prev_sample=out)
+
+    add_noise_coeffs = DDIMScheduler.add_noise_coeffs
+    add_noise = DDIMScheduler.add_noise          # sqrt(a_t) x0 + sqrt(1 - a_t) noise: the same forward process, one shared implementation

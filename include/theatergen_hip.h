@@ -155,9 +155,13 @@ int tg_gemm(const tg_gemm_desc* d, void* stream);
 int64_t tg_gemm_workspace_bytes(const tg_gemm_desc* d);
 /* the tile (tokens x channels), the K-split of the tail tiles (1 = none) and the kernel (0 = GEMM, 1 = implicit-GEMM
  * conv, 2 = LDS-halo conv, 3 = big-tile persistent GEMM, 4 = slab conv (128 x 320 tiles, loader + compute waves, optional
- * GroupNorm prologue), 5 = loader / compute GEMM (128 x 320 tiles, long K), 6 = LayerNorm-fused projection (ln_u)) the heuristic
- * picks for a descriptor */
+ * GroupNorm prologue), 6 = LayerNorm-fused projection (ln_u), 7 = ping-pong persistent GEMM (256 x 256 / 256 x 160 tiles); there is no 5)
+ * the heuristic picks for a descriptor */
 int tg_gemm_plan(const tg_gemm_desc* d, int32_t* tile_m, int32_t* tile_n, int32_t* splits, int32_t* kernel_kind);
+/* the name of the kernel template tg_gemm launches for `d` ("gemm_glds_kernel", "conv_halo_kernel", "bt_gemm_kernel", "conv_slab_kernel",
+ * "conv_slab_pp_kernel", "pp_gemm_kernel", "pp160_gemm_kernel"): a static string, NULL for a descriptor tg_gemm_plan rejects.  What profilers label a
+ * launch with.  Additive to ABI 308: one new symbol, tg_gemm_desc unchanged, TG_ABI_VERSION unchanged. */
+const char* tg_gemm_kernel_name(const tg_gemm_desc* d);
 /* > 0: the kernel tg_gemm runs for `d` can write GroupNorm(d->out_gn_groups) partial sums of its output (tg_gemm_desc.out_gn_partials); the value is the number
  * of 64-pixel blocks per batch item (the `nblk` of tg_groupnorm_from_partials).  0: it cannot (ask before setting out_gn_partials). */
 int tg_gemm_gn_partial_blocks(const tg_gemm_desc* d);

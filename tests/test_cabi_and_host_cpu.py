@@ -352,7 +352,8 @@ def test_static_slots_identity_is_the_object_not_the_address():
 
 def test_gemm_planner_kernel_choice(monkeypatch):
     """tg_gemm_plan is host logic: which kernel / tile / split a descriptor gets (no launch, works without a GPU).
-    kernel_kind: 0 GEMM, 1 implicit-GEMM conv, 2 LDS-halo conv, 3 big-tile GEMM, 4 slab conv (GroupNorm prologue), 5 loader / compute GEMM."""
+    kernel_kind: 0 GEMM, 1 implicit-GEMM conv, 2 LDS-halo conv, 3 big-tile GEMM, 4 slab conv (GroupNorm prologue), 6 LayerNorm-fused projection,
+    7 ping-pong GEMM (there is no 5).  tg_gemm_kernel_name: the kernel template behind that choice."""
     import ctypes as C
     from theatergen_amd import _lib
     h = _lib.lib()
@@ -450,6 +451,31 @@ def test_gemm_planner_kernel_choice(monkeypatch):
     assert plan(gemm(16384, 640, 2560))[:2] == (128, 128)
     monkeypatch.delenv("TG_T160")
     monkeypatch.delenv("TG_PP")
+
+    # the kernel template's name: what ops.gemm labels a profiled launch with (bench.py groups its roofline by these)
+    def name(d):
+        got = h.tg_gemm_kernel_name(C.byref(d))
+        return got.decode() if got is not None else None
+    monkeypatch.delenv("TG_SLAB_PP", raising=False)
+    assert name(conv(16, 64, 64, 320, 320)) == "conv_slab_pp_kernel"          # two compute waves per SIMD on whole 64-wide rows
+    assert plan(conv(2, 96, 96, 320, 320))[3] == 4 and name(conv(2, 96, 96, 320, 320)) == "conv_slab_pp_kernel"      # ... and on 32-wide patches of a 96-wide map
+    assert plan(conv(2, 24, 24, 1280, 1280))[3] == 4 and name(conv(2, 24, 24, 1280, 1280)) == "conv_slab_kernel"     # two 8 x 8 patches per tile: one-wave kernel
+    monkeypatch.setenv("TG_SLAB_PP", "2")                                      # no two-wave kernel on patch tiles
+    assert name(conv(2, 96, 96, 320, 320)) == "conv_slab_kernel" and name(conv(16, 64, 64, 320, 320)) == "conv_slab_pp_kernel"
+    monkeypatch.setenv("TG_SLAB_PP", "0")
+    assert name(conv(16, 64, 64, 320, 320)) == "conv_slab_kernel"
+    monkeypatch.delenv("TG_SLAB_PP")
+    assert name(gemm(16384, 640, 2560)) == "pp160_gemm_kernel" and name(gemm(4096, 10240, 1280)) == "pp_gemm_kernel"
+    assert name(gemm(65536, 2560, 320, geglu=1)) == "bt_gemm_kernel"
+    ln = gemm(4096, 1280, 1280)
+    ln.ln_u, ln.ln_v, ln.ln_eps = 64, 64, 1e-5
+    assert plan(ln)[3] == 6 and name(ln) == "gemm_glds_kernel"
+    assert plan(conv(16, 64, 64, 320, 320, stride=2))[3] == 1 and name(conv(16, 64, 64, 320, 320, stride=2)) == "gemm_glds_kernel"
+    assert plan(conv(16, 8, 8, 1280, 1280))[3] == 2 and name(conv(16, 8, 8, 1280, 1280)) == "conv_halo_kernel"
+    assert name(gemm(65536, 320, 320)) == "gemm_glds_kernel" and name(gemm(256, 64, 128, force_tile=0)) == "gemm_glds_kernel"
+    bad = gemm(256, 64, 128)
+    bad.a0 = 24
+    assert name(bad) is None and b"16-byte aligned" in h.tg_last_error()
 
 
 def test_shift_tensor_ignore_last_dim_matches_reference_formula():

@@ -1,5 +1,5 @@
-"""GPU: the branches tg_gemm takes on operand alignment and pitch (tg_gemm.hip::epi_lds_of, pp_eligible / pp160_eligible,
-tg_conv_slab_is_pp, gn_partial_blocks_of), which the production plans never reach: out / res / bias / bvec 8-byte (not 16-byte) aligned,
+"""GPU: the branches tg_gemm takes on operand alignment and pitch (tg_gemm_route.hip::epi_lds_of, pp_eligible,
+slab_two_wave, slab_gn_partial_blocks), which the production plans never reach: out / res / bias / bvec 8-byte (not 16-byte) aligned,
 ldc / ldres / ldbvec odd multiples of 4, an n_split that is a multiple of 4 but not of 64.  Every launch goes through
 ``tests.launch_check`` (fp64 contract reference, read extents, overlap, stray writes, NaN replay).  Only descriptors the validator accepts
 are launched; a0 / a1 / w, the workspace and the LayerNorm vectors stay 16-byte aligned."""

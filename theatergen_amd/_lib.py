@@ -135,6 +135,7 @@ SIGNATURES = {
     "tg_gemm": (i32, [C.POINTER(GemmDesc), vp]),
     "tg_gemm_workspace_bytes": (i64, [C.POINTER(GemmDesc)]),
     "tg_gemm_plan": (i32, [C.POINTER(GemmDesc), vp, vp, vp, vp]),
+    "tg_gemm_kernel_name": (C.c_char_p, [C.POINTER(GemmDesc)]),
     "tg_attention": (i32, [C.POINTER(AttnDesc), vp]),
     "tg_attention_wide": (i32, [C.POINTER(AttnDesc), vp]),
     "tg_attention_bwd": (i32, [C.POINTER(AttnBwdDesc), vp]),

@@ -1,6 +1,6 @@
 // 3x3 convolution for the 320-multiple channel counts of the SD UNets: one output tile = 128 pixels x 320 output channels per
 // workgroup, the input window staged ONCE per 320 channels, GroupNorm(+SiLU) applied while it is staged
-// (include/theatergen_hip.h: tg_gemm mode 1, selected by the planner in tg_gemm.hip; replaces the conv1 / conv2 +
+// (include/theatergen_hip.h: tg_gemm mode 1, selected by the planner in tg_gemm_route.hip; replaces the conv1 / conv2 +
 // nonlinearity(norm(x)) pairs of ResnetBlock2D, models/resnet.py via models/unet_2d_blocks.py:184-195).
 //
 // Why a second conv kernel.  conv_halo_kernel (tg_gemm.hip) gives every 128-channel output tile its own workgroup: N = 320
@@ -455,7 +455,7 @@ int launch_slab(const tg_gemm_desc* d, GemmParams p, int splits, hipStream_t st)
 
 template <typename T>
 int launch_slab_dtype(const tg_gemm_desc* d, const GemmParams& p, int splits, hipStream_t st) {
-  // the planner (tg_gemm.hip: slab_geometry) chose the patch width / patches per tile: whole rows of 64 / 32 / 16-wide maps, patches of
+  // the planner (tg_gemm_route.hip: slab_geometry) chose the patch width / patches per tile: whole rows of 64 / 32 / 16-wide maps, patches of
   // wider maps (128 = 2 x 64, 96 = 3 x 32, 48 = 3 x 16, ...), two 8 x 8 patches for the 8- / 24- / 40-wide maps
   const bool patch = p.patch_pwl > 0;
   const int pw = patch ? (1 << p.patch_pwl) : d->out_w;
@@ -480,25 +480,12 @@ int launch_slab_dtype(const tg_gemm_desc* d, const GemmParams& p, int splits, hi
 // ping-pong compute waves (tg_conv_slab_pp.hip, round 6): whole-row tiles of the 64 / 32 / 16-wide maps
 int tg_conv_slab_pp_launch(const tg_gemm_desc* d, const void* params, int splits, void* stream);
 
-// Called by tg_gemm.hip's planner (not part of the C ABI); GemmParams arrives filled except for the tile bookkeeping.  With
+// Called by tg_gemm.hip (not part of the C ABI); GemmParams arrives filled except for the tile bookkeeping.  With
 // splits > 1 the caller runs the reduce kernel over the tiles_m * tiles_n tail tiles of `splits` partials each.
-// TG_SLAB_PP (dev A/B knob): 0 keeps every layer on conv_slab_kernel (one compute wave per SIMD), 1 = the two-waves-per-SIMD kernel on the 64-wide
-// maps only, 2 = on the 32- and 16-wide maps as well, 3 (default) = also on the 64 / 32 / 16-wide PATCH tiles of wider maps.  Isolated launches (scripts/dev_slab_pp.py): 64 x 64 layers 4-6 % faster, 32 x 32 equal,
-// 16 x 16 (split tiles) 5-10 % slower; under graph replay, same box, interleaved (profiles/r6_ab_slab2w.json): 864.3 -> 859.3 (mode 1) -> 855.3 ms per
-// story (mode 2, +1.05 %): the whole-step evidence decides.
-bool tg_conv_slab_is_pp(const tg_gemm_desc* d, int patch_pwl, int patch_np, int epi_lds) {
-  const char* e = getenv("TG_SLAB_PP");
-  const int mode = e == nullptr ? 3 : (int)strtol(e, nullptr, 0);
-  // tile width: the whole row, or (round 6, TG_SLAB_PP >= 3 = default) one patch of a wider map (SD-2.1's 96 / 48-wide, SDXL's 128-wide levels)
-  const int pw = patch_pwl > 0 ? (1 << patch_pwl) : d->out_w;
-  if (patch_pwl > 0 && mode < 3) return false;
-  const bool w_ok = pw == 64 || (mode >= 2 && (pw == 32 || pw == 16));
-  return mode >= 1 && w_ok && patch_np == 1 && epi_lds && d->in_w == d->out_w;
-}
-
-int tg_conv_slab_launch(const tg_gemm_desc* d, const void* params, int splits, void* stream) {
+// two_wave (the planner's choice, tg_gemm_route.hip: TG_SLAB_PP): conv_slab_pp_kernel, two compute waves per SIMD, instead of conv_slab_kernel.
+int tg_conv_slab_launch(const tg_gemm_desc* d, const void* params, int splits, bool two_wave, void* stream) {
   const GemmParams& p = *reinterpret_cast<const GemmParams*>(params);
-  if (tg_conv_slab_is_pp(d, p.patch_pwl, p.patch_np, p.epi_lds)) return tg_conv_slab_pp_launch(d, params, splits, stream);
+  if (two_wave) return tg_conv_slab_pp_launch(d, params, splits, stream);
   TG_CHECK(p.gn_part == nullptr, TG_ERR_UNSUPPORTED, "tg_gemm conv: out_gn_partials needs the two-wave slab kernel (tg_gemm_gn_partial_blocks)");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (d->dtype == TG_BF16) return launch_slab_dtype<bf16_t>(d, p, splits, st);

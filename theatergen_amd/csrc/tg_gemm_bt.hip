@@ -1,4 +1,4 @@
-// Big-tile MFMA GEMM for gfx950 ("bt" kernels; include/theatergen_hip.h: tg_gemm, selected by the planner in tg_gemm.hip).
+// Big-tile MFMA GEMM for gfx950 ("bt" kernels; include/theatergen_hip.h: tg_gemm, selected by the planner in tg_gemm_route.hip).
 //
 // Why a second kernel family.  The 128x128 kernels of tg_gemm.hip move 32 KB of operands from L2 into LDS per 2 * 128 * 128 * 64
 // FLOP: at the MFMA peak that is 64 B/clk per CU = 39 TB/s over the chip, MORE than the 34.5 TB/s the eight L2s deliver

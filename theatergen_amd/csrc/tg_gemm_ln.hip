@@ -24,7 +24,7 @@ int launch_ln(const GemmParams& p, int grid, hipStream_t st) {
   return p.ln_rows != nullptr ? launch_ln_mode<T, STAGES, BKT, EPI, 2>(p, grid, st) : launch_ln_mode<T, STAGES, BKT, EPI, 1>(p, grid, st);
 }
 
-// round 5: 128 x 160 tiles (four waves of 32 tokens x 160 channels) where they fill whole rounds of the chip and 128 x 128 does not (tg_gemm.hip: make_plan):
+// round 5: 128 x 160 tiles (four waves of 32 tokens x 160 channels) where they fill whole rounds of the chip and 128 x 128 does not (tg_gemm_route.hip: make_plan):
 // attn2.to_q of the 32 x 32 / 16 x 16 levels (16384 x 640, 4096 x 1280: 512 / 256 tiles) and attn1's q | k | v at 32 x 32 (16384 x 1920: 1536 = 3 x 512)
 template <typename T, int STAGES, int MODE>
 int launch_ln160_mode(const GemmParams& p, int grid, hipStream_t st) {

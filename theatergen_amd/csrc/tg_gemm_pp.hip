@@ -1,4 +1,4 @@
-// "Ping-pong" MFMA GEMM for gfx950 (round 6; include/theatergen_hip.h: tg_gemm, selected by the planner in tg_gemm.hip — pp_variant_of).
+// "Ping-pong" MFMA GEMM for gfx950 (round 6; include/theatergen_hip.h: tg_gemm, selected by the planner in tg_gemm_route.hip — pp_selected).
 //
 // Why a third plain-GEMM kernel.  The LDS-DMA kernels of tg_gemm_glds.h (128 x 128 / 128 x 160, four waves) and the lock-step big tile of
 // tg_gemm_bt.hip top out at 0.85 - 1.0 PFLOP/s on random bf16 although the matrix pipe alone sustains 1.88 PFLOP/s on the same data and the

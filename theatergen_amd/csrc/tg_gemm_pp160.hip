@@ -1,4 +1,4 @@
-// Ping-pong MFMA GEMM on 256 x 160 tiles (round 6; planner: tg_gemm.hip pp160_selected, force_tile 25) — tg_gemm_pp.hip's structure for the UNet's
+// Ping-pong MFMA GEMM on 256 x 160 tiles (round 6; planner: tg_gemm_route.hip pp_selected, force_tile 25) — tg_gemm_pp.hip's structure for the UNet's
 // N = 640 / 1920 projections, whose tile COUNT (round 5, tg_gemm_t160.hip) only works out on 160-column tiles: 16384 x 640 is 256 tiles of 256 x 160 =
 // exactly one per CU, 16384 x 1920 is 768 = three rounds.
 //   * tile 256 x 160 x 64, 8 waves = 4 (M) x 2 (N), wave tile 64 x 80 = 4 x 5 MFMA tiles of 16 x 16 x 32 (80 accumulator registers), issued "swapped":

@@ -1,7 +1,7 @@
 // gemm_glds_kernel on 128 x 160 tiles (round 5; own translation unit: compile time).  Plain GEMM, linear epilogue (bias / per-batch vector / residual / scale).
 // Four waves of 32 token rows x 160 channels (1 x 5 MFMA tiles per wave, fragments read per k-step).  What the shape is for is the TILE COUNT of the UNet's
 // mid-level projections (M x N = 16384 x 640 and 4096 x 1280: models/attention.py:186-236 to_out / net.2, models/transformer_2d.py:285-327 proj_in / proj_out):
-// 512 / 256 tiles = exactly two / one per CU, where 128 x 128 gives 640 / 320 tiles on 768 / 512 co-resident slots (tg_gemm.hip: make_plan).
+// 512 / 256 tiles = exactly two / one per CU, where 128 x 128 gives 640 / 320 tiles on 768 / 512 co-resident slots (tg_gemm_route.hip: make_plan).
 #include "tg_gemm_glds.h"
 
 namespace {

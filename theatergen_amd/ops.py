@@ -156,23 +156,10 @@ def gemm(a0, w, M, N, K, *, mode=0, a1=None, c0=None, c1=0, conv=None, bias=None
     e0.record()
     launch()
     e1.record()
-    if kk.value == 2:
-        kname = "conv_halo_kernel<128x128>"
-    elif kk.value == 4:
-        # round 6: tiles of one 64 / 32 / 16-wide patch — the whole row or a patch of a wider map — run on conv_slab_pp_kernel (csrc/tg_conv_slab.hip: TG_SLAB_PP, default 3)
-        spp = os.environ.get("TG_SLAB_PP", "3")
-        ow = int(conv[4]) if conv is not None else 0
-        pw = ow if ow in (16, 32, 64) else (64 if ow % 64 == 0 else 32 if ow % 32 == 0 else 16 if ow % 16 == 0 else 8)
-        two_wave = ((pw == 64 and spp != "0") or (pw in (16, 32) and spp not in ("0", "1"))) and (pw == ow or spp not in ("0", "1", "2"))
-        kname = ("conv_slab_pp_kernel" if two_wave and int(conv[2]) == ow else "conv_slab_kernel") + f"<{tm.value}x{tn.value}>" + ("+gn" if a_coef is not None else "")
-    elif kk.value == 3:
-        kname = f"bt_gemm_kernel<{tm.value}x{tn.value}>"
-    elif kk.value == 6:
-        kname = f"gemm_glds_kernel<plain+ln,{tm.value}x{tn.value}>"
-    elif kk.value == 7:
-        kname = ("pp160_gemm_kernel" if tn.value == 160 else "pp_gemm_kernel") + f"<{tm.value}x{tn.value}" + (",geglu" if geglu else "") + (",ln" if ln is not None else "") + ">"
-    else:
-        kname = f"gemm_glds_kernel<{'conv' if mode == 1 else 'plain'},{tm.value}x{tn.value}>"
+    # label = the kernel template the planner names + the variant / tile as the profiles have always spelled them (bench.py groups by these strings)
+    variant = {0: "plain,", 1: "conv,", 6: "plain+ln,"}.get(kk.value, "")
+    tail = ((",geglu" if geglu else "") + (",ln" if ln is not None else "")) if kk.value == 7 else ""
+    kname = f"{L.tg_gemm_kernel_name(C.byref(d)).decode()}<{variant}{tm.value}x{tn.value}{tail}>" + ("+gn" if kk.value == 4 and a_coef is not None else "")
     _gemm_profile.append(dict(kernel=kname, splits=sp.value,
                               M=int(M), N=int(N), K=int(K), flops=2.0 * M * N * K, events=(e0, e1),
                               has_res=res is not None, n_out=int(n_main if n_split <= 0 else N)))
@@ -626,6 +613,31 @@ def conv3x3_takes_gn(dtype, batch, in_h, in_w, cin, c1, cout):
         kk = C.c_int32()
         hit = L.tg_gemm_plan(C.byref(d), None, None, None, C.byref(kk)) == 0 and kk.value == 4
         _slab_plans[key] = hit
+    return hit
+
+
+_ln_pp_plans = {}
+
+
+def ln_qkv_takes_stats(dtype, M, C_, K, rows_per_batch):
+    """True when tg_gemm runs the LayerNorm-folded q | k | v^T projection ([M, K] -> Q | K [M, 2 C] + V^T [M / rows, C, rows]) on the ping-pong tiles
+    (tg_gemm_plan kernel_kind 7), which fold the norm from PRECOMPUTED row statistics: the caller runs ``layernorm_stats`` first.  Asked of the planner with
+    the descriptor ``AttnProcessor`` launches (plan only, as ``conv3x3_takes_gn``)."""
+    key = (dtype, M, C_, K, rows_per_batch, os.environ.get("TG_PP"))
+    hit = _ln_pp_plans.get(key)
+    if hit is None:
+        d = GemmDesc()
+        d.dtype = 0 if dtype == torch.bfloat16 else 1
+        d.a0 = d.w = d.out = d.out_t = 16                   # plan only: pointers are not dereferenced, just non-NULL and aligned
+        d.ln_u = d.ln_v = d.ln_rows = 16
+        d.ln_eps = 1e-5
+        d.c0 = d.K = int(K)
+        d.M, d.N = int(M), 3 * int(C_)
+        d.rows_per_batch, d.n_split, d.ldc, d.ldt = int(rows_per_batch), 2 * int(C_), 2 * int(C_), (int(rows_per_batch) + 7) // 8 * 8
+        d.out_scale = 1.0
+        kk = C.c_int32()
+        hit = _lib.lib().tg_gemm_plan(C.byref(d), None, None, None, C.byref(kk)) == 0 and kk.value == 7
+        _ln_pp_plans[key] = hit
     return hit
 
 

@@ -5,7 +5,8 @@ see the same clocks and the same neighbours; median, min and max of the rounds a
 
  (a) the step-epilogue launch alone at the flagship shape (8 x 4 x 64 x 64 latents, CFG, history row, bf16 model input, counter advanced): 50 launches
      captured in one graph per route, ms per replay / 50.  Bytes per element: DDIM reads u, c, x and writes x, the history row and two bf16 model inputs
-     = 24; DPM also reads and rewrites the fp32 state = 32.
+     = 24; DPM also reads and rewrites the fp32 state = 32; Euler ancestral also reads its bf16 noise row = 26 (timed beside them by the same method,
+     so all three instances of the one kernel body are covered).
  (b) ms per replayed step of the 8-image engine (SD-1.5 plan, seeded random weights, 50 steps each): the UNet is the same, only the epilogue differs.
  (c) the 8-image story: 50 DDIM steps against 25 DPM steps, time only.
 
@@ -31,7 +32,7 @@ import torch  # noqa: E402
 
 from theatergen_amd import config, ops, weights  # noqa: E402
 from theatergen_amd.pipelines import DenoiseEngine  # noqa: E402
-from theatergen_amd.scheduler import DDIMScheduler, DPMSolverMultistepScheduler  # noqa: E402
+from theatergen_amd.scheduler import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler  # noqa: E402
 from theatergen_amd.unet import UNet2DConditionModel  # noqa: E402
 
 DEV = "cuda:0"
@@ -80,16 +81,17 @@ def alternate(routes, rounds, warm=2):
 def epilogue_launch(rounds, g, steps=50):
     shape = (N_IMG, C_, HW, HW)
     noise_pred = torch.randn((2 * N_IMG, C_, HW, HW), generator=g).to(DEV)
-    ddim, dpm = DDIMScheduler(), DPMSolverMultistepScheduler()
-    ddim.set_timesteps(steps)
-    dpm.set_timesteps(steps)
+    ddim, dpm, euler_a = DDIMScheduler(), DPMSolverMultistepScheduler(), EulerAncestralDiscreteScheduler()
+    for s in (ddim, dpm, euler_a):
+        s.set_timesteps(steps)
     # every buffer a captured launch addresses stays referenced from `bufs` until the timing is over: a graph holds raw addresses, and entering
     # `torch.cuda.graph` empties the allocator's cache, which would hand a dropped tensor of an earlier capture back to the driver
     bufs = {}
-    for name, coef in (("ddim", ddim.coef_table()), ("dpm", dpm.coef_table())):
+    for name, coef in (("ddim", ddim.coef_table()), ("dpm", dpm.coef_table()), ("euler_a", euler_a.coef_table())):
         bufs[name] = dict(coef=coef.to(DEV), lat=torch.randn(shape, generator=g).to(DEV), state=torch.zeros(shape, device=DEV),
                           idx=torch.zeros(1, dtype=torch.int32, device=DEV), hist=torch.zeros((steps + 1,) + shape, device=DEV),
                           model_in=torch.zeros((2 * N_IMG, C_, HW, HW), dtype=DTYPE, device=DEV))
+    bufs["euler_a"]["noise"] = torch.randn((steps,) + shape, generator=g).to(DEV, DTYPE)
 
     def chain(name):
         b = bufs[name]
@@ -97,9 +99,12 @@ def epilogue_launch(rounds, g, steps=50):
         for _ in range(steps):
             if name == "ddim":
                 ops.step_epilogue(noise_pred, b["lat"], 7.5, b["coef"], b["idx"], advance=True, history=b["hist"], model_in=b["model_in"])
-            else:
+            elif name == "dpm":
                 ops.step_epilogue_dpm(noise_pred, b["lat"], b["state"], 7.5, b["coef"], b["idx"], advance=True, history=b["hist"],
                                       model_in=b["model_in"])
+            else:
+                ops.step_epilogue_sigma(noise_pred, b["lat"], 7.5, b["coef"], b["idx"], advance=True, noise=b["noise"], history=b["hist"],
+                                        model_in=b["model_in"])
     graphs = {}
     for name in bufs:
         s = torch.cuda.Stream(device=DEV)
@@ -117,7 +122,7 @@ def epilogue_launch(rounds, g, steps=50):
         for k in ("median_ms", "min_ms", "max_ms"):
             v[k.replace("_ms", "_us_per_step")] = v[k] * 1e3 / steps
     r["dpm_over_ddim"] = r["dpm"]["median_ms"] / r["ddim"]["median_ms"]
-    r["bytes_per_element"] = {"ddim": 24, "dpm": 32}
+    r["bytes_per_element"] = {"ddim": 24, "dpm": 32, "euler_a": 26}
     r["elements"] = N_IMG * C_ * HW * HW
     torch.cuda.synchronize()
     del graphs                                             # before the buffers they address
@@ -185,7 +190,8 @@ def markdown(res):
          "Bytes moved per element: 24 (DDIM) against 32 (DPM: the fp32 state is read and rewritten), so <= 1.33x is what the traffic predicts.", "",
          "| route | us per step | spread of the rounds |", "|---|---|---|",
          f"| `tg_step_epilogue` (DDIM) | {fmt(a['ddim'], 'median_us_per_step')} | {a['ddim']['spread']:.1%} |",
-         f"| `tg_step_epilogue_dpm` | {fmt(a['dpm'], 'median_us_per_step')} | {a['dpm']['spread']:.1%} |", "",
+         f"| `tg_step_epilogue_dpm` | {fmt(a['dpm'], 'median_us_per_step')} | {a['dpm']['spread']:.1%} |",
+         f"| `tg_step_epilogue_sigma` (Euler ancestral, bf16 noise row: 26 bytes) | {fmt(a['euler_a'], 'median_us_per_step')} | {a['euler_a']['spread']:.1%} |", "",
          f"DPM / DDIM = {a['dpm_over_ddim']:.3f}.  A step is the epilogue launch plus the one-thread counter launch that both routes make.",
          "At about 4 us for 3-4 MB both launches are set by launch latency rather than by HBM traffic, which is why the ratio stays under what the bytes predict.", "",
          "## (b) ms per replayed step, 8-image engine (SD-1.5 plan, bf16, 50 steps each)", "",
@@ -218,6 +224,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--md", default=None)
     ap.add_argument("--parity", default=None)
+    ap.add_argument("--epilogue-only", action="store_true", help="section (a) alone, as JSON to --out: for many short runs interleaved between two builds")
     args = ap.parse_args()
     if args.rounds < 5:
         raise SystemExit("dpm_step_timing.py: at least 5 rounds")
@@ -234,6 +241,12 @@ def main():
     with section("epilogue launch", args.limit):
         res["epilogue"] = epilogue_launch(args.rounds, g)
         print(json.dumps(res["epilogue"]), flush=True)
+    if args.epilogue_only:
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     with section("8-image engines", args.limit):
         res["per_step"], res["story"], res["dpm25_finite"] = engines(args.rounds, g)
         print(json.dumps({"per_step": res["per_step"], "story": res["story"]}), flush=True)

@@ -158,6 +158,9 @@ HOT_GATES = [
     ("pp_gemm_kernel<", 256, 256),
     ("conv_in_mfma_kernel<", 0, 256),                              # round 5: boundary convs on the matrix cores
     ("conv_out_mfma_kernel<", 0, 128),
+    # the step epilogue, one body for every sampler (tg_step.hip; <DdimUpdate>, <SigmaUpdate>, <DpmUpdate>).  40 VGPRs is the largest of the three
+    # hand-written kernels it replaced (22 / 40 / 22): a policy that pushes the shared body past that, or into scratch, has changed more than its arithmetic
+    ("step_epilogue_kernel<", 0, 40),
 ]
 
 
@@ -178,6 +181,10 @@ def _pretty(sym):
             args.append("bf16"); i += 5
         elif rest.startswith("DF16_", i):
             args.append("f16"); i += 5
+        elif rest.startswith("NS_", i):                               # a class of the file's anonymous namespace: NS_<length><name>E
+            m = re.match(r"NS_(\d+)", rest[i:])
+            j = i + m.end() + int(m.group(1))
+            args.append(rest[i + m.end():j]); i = j + 1
         elif rest[i] == "L":
             j = rest.index("E", i)
             tok = rest[i + 1:j]

@@ -84,6 +84,12 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// blocks of 256 threads for a one-thread-per-element launch over n elements, capped at 2048: the kernels loop grid-stride beyond that
+inline int tg_blocks_1d(long n) {
+  const long b = (n + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+}
+
 // ---- host-side error plumbing (tg_api.hip) -------------------------------------------------------
 void tg_set_error(const char* fmt, ...);
 #define TG_CHECK(cond, code, ...)            \

@@ -1,6 +1,6 @@
 // Elementwise / boundary kernels (HBM- or latency-bound): GEGLU gate, activations, residual add,
 // conv_in / conv_out (tiny channel counts, NCHW <-> token-major conversion folded in), sinusoidal
-// timestep embedding, the fused CFG + DDIM + frozen-mask step epilogue, latent blend / shift / compose.
+// timestep embedding, latent blend / shift / compose.  (The step epilogue is tg_step.hip.)
 #include "tg_common.h"
 
 namespace {
@@ -138,65 +138,6 @@ __global__ void timestep_embedding_kernel(const float* t, const int* index, int 
   }
 }
 
-struct StepParams {
-  const float* noise_pred;
-  float* latents;
-  int n_img, chw, hw;
-  int has_cfg;
-  float g;
-  const float* coef;
-  int* step_idx;
-  int advance;
-  int pred_type;
-  const float* frozen;
-  const float* frozen_mask;
-  int mask_per_img;
-  int frozen_steps;
-  float* history;
-  void* model_in;
-  int model_in_dtype;
-};
-
-__global__ __launch_bounds__(256) void step_epilogue_kernel(StepParams p) {
-  const int step = *p.step_idx;
-  const float sa = p.coef[step * 4], sb = p.coef[step * 4 + 1], sap = p.coef[step * 4 + 2], sbp = p.coef[step * 4 + 3];
-  const long total = (long)p.n_img * p.chw;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const float u = p.noise_pred[i];
-    float mo = u;
-    if (p.has_cfg) { const float c = p.noise_pred[total + i]; mo = u + p.g * (c - u); }
-    const float x = p.latents[i];
-    float x0, eps;
-    if (p.pred_type == 0) { x0 = (x - sb * mo) / sa; eps = mo; }
-    else { x0 = sa * x - sb * mo; eps = sa * mo + sb * x; }
-    float nx = sap * x0 + sbp * eps;
-    if (p.frozen && step < p.frozen_steps) {
-      const long img = i / p.chw;
-      const long pix = (i - img * p.chw) % p.hw;
-      const float m = p.frozen_mask[(p.mask_per_img ? img * p.hw : 0) + pix];
-      const float f = p.frozen[(long)(step + 1) * total + i];
-      nx = f * m + nx * (1.f - m);
-    }
-    p.latents[i] = nx;
-    if (p.history) p.history[(long)(step + 1) * total + i] = nx;
-    if (p.model_in) {
-      // next UNet input = cat([latents] * 2) in the model dtype (models/pipelines.py:409-414)
-      if (p.model_in_dtype == TG_BF16) {
-        reinterpret_cast<bf16_t*>(p.model_in)[i] = (bf16_t)nx;
-        reinterpret_cast<bf16_t*>(p.model_in)[total + i] = (bf16_t)nx;
-      } else if (p.model_in_dtype == TG_F16) {
-        reinterpret_cast<f16_t*>(p.model_in)[i] = (f16_t)nx;
-        reinterpret_cast<f16_t*>(p.model_in)[total + i] = (f16_t)nx;
-      } else {
-        reinterpret_cast<float*>(p.model_in)[i] = nx;
-        reinterpret_cast<float*>(p.model_in)[total + i] = nx;
-      }
-    }
-  }
-}
-
-__global__ void step_advance_kernel(int* step_idx) { *step_idx += 1; }
-
 // ROUND: 0 = fp32 latents (the reference with an fp32 UNet); 1 / 2 = the reference's arithmetic when the latents are
 // fp16 / bf16 tensors (utils/latents.py:156-166 with dtype = unet.dtype, generate.py:77-81): `bg * sqrt(1-r)`,
 // `fg * sqrt(r)` and their sum are half-precision tensor ops (each computed in fp32 and rounded to the storage type),
@@ -317,12 +258,7 @@ __global__ __launch_bounds__(256) void transpose_big_kernel(const T* src, int ro
   }
 }
 
-inline int grid_for(long n, int per_thread = 1) {
-  long b = (n / per_thread + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > 2048) b = 2048;
-  return (int)b;
-}
+inline int grid_for(long n, int per_thread = 1) { return tg_blocks_1d(n / per_thread); }
 
 // ---- fast paths for the UNet's two thin convolutions (the generic kernels above stay as the fallback) -----------
 // conv_in (4 -> 320 at SD-1.5): fp32 weights transposed to [K][cout] in LDS once per (persistent) block; a thread owns
@@ -957,27 +893,6 @@ extern "C" int tg_timestep_embedding(int32_t dtype, const float* t, const int32_
   else
     hipLaunchKernelGGL(timestep_embedding_kernel<f16_t>, dim3(rows), dim3(128), 0, st, t, index, t_stride, rows, dim, flip_sin_to_cos, freq_shift, (f16_t*)out, ldo);
   TG_LAUNCH_CHECK();
-  return TG_OK;
-}
-
-extern "C" int tg_step_epilogue(const float* noise_pred, float* latents, int32_t n_img, int32_t chw, int32_t hw,
-                                int32_t has_cfg, float guidance_scale, const float* coef, int32_t* step_idx, int32_t advance,
-                                int32_t prediction_type, const float* frozen, const float* frozen_mask,
-                                int32_t mask_per_img, int32_t frozen_steps, float* history, void* model_in,
-                                int32_t model_in_dtype, void* stream) {
-  TG_CHECK(noise_pred && latents && coef && step_idx && n_img > 0 && chw > 0 && hw > 0 && chw % hw == 0, TG_ERR_ARG,
-           "tg_step_epilogue: bad args");
-  TG_CHECK(prediction_type == 0 || prediction_type == 1, TG_ERR_ARG, "tg_step_epilogue: bad prediction type");
-  TG_CHECK(!frozen || frozen_mask, TG_ERR_ARG, "tg_step_epilogue: frozen latents need a mask");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  StepParams p{noise_pred, latents, n_img, chw, hw, has_cfg, guidance_scale, coef, step_idx, advance, prediction_type, frozen,
-               frozen_mask, mask_per_img, frozen_steps, history, model_in, model_in_dtype};
-  hipLaunchKernelGGL(step_epilogue_kernel, dim3(grid_for((long)n_img * chw)), dim3(256), 0, st, p);
-  TG_LAUNCH_CHECK();
-  if (advance) {
-    hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, st, step_idx);
-    TG_LAUNCH_CHECK();
-  }
   return TG_OK;
 }
 

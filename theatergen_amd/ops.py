@@ -840,51 +840,44 @@ def timestep_embedding(t_dev, rows, dim, flip_sin_to_cos, freq_shift, dtype, t_s
     return out
 
 
-def step_epilogue(noise_pred, latents, guidance_scale, coef, step_idx, *, has_cfg=True, advance=True, prediction_type=0, frozen=None,
-                  frozen_mask=None, frozen_steps=0, history=None, model_in=None):
+def _step_epilogue(entry, noise_pred, latents, guidance_scale, coef, step_idx, has_cfg, advance, frozen, frozen_mask, frozen_steps, history, model_in,
+                   state=(), own=()):
+    """What the three step epilogues share (csrc/tg_step.hip): the geometry read off ``latents`` and the pointer marshalling.  ``state``: the entry
+    point's own leading arguments after ``latents``; ``own``: its own arguments after ``advance``."""
     n_img = latents.shape[0]
     chw = latents[0].numel()
     hw = latents.shape[-1] * latents.shape[-2]
     mask_per_img = 1 if (frozen_mask is not None and frozen_mask.numel() == n_img * hw and n_img > 1) else 0
     mi_dt = -1 if model_in is None else _SRC[model_in.dtype]
-    _lib.check(_lib.lib().tg_step_epilogue(_ptr(noise_pred), _ptr(latents), n_img, chw, hw, 1 if has_cfg else 0, float(guidance_scale), _ptr(coef),
-                                           _ptr(step_idx), 1 if advance else 0, prediction_type, _ptr(frozen), _ptr(frozen_mask),
-                                           mask_per_img, int(frozen_steps), _ptr(history), _ptr(model_in), mi_dt, _stream()))
+    _lib.check(getattr(_lib.lib(), entry)(_ptr(noise_pred), _ptr(latents), *state, n_img, chw, hw, 1 if has_cfg else 0, float(guidance_scale), _ptr(coef),
+                                          _ptr(step_idx), 1 if advance else 0, *own, _ptr(frozen), _ptr(frozen_mask), mask_per_img, int(frozen_steps),
+                                          _ptr(history), _ptr(model_in), mi_dt, _stream()))
+
+
+def step_epilogue(noise_pred, latents, guidance_scale, coef, step_idx, *, has_cfg=True, advance=True, prediction_type=0, frozen=None,
+                  frozen_mask=None, frozen_steps=0, history=None, model_in=None):
+    _step_epilogue("tg_step_epilogue", noise_pred, latents, guidance_scale, coef, step_idx, has_cfg, advance, frozen, frozen_mask, frozen_steps, history,
+                   model_in, own=(prediction_type,))
 
 
 def step_epilogue_sigma(noise_pred, latents, guidance_scale, coef, step_idx, *, has_cfg=True, advance=True, noise=None, frozen=None,
                         frozen_mask=None, frozen_steps=0, history=None, model_in=None):
     """Euler / Euler-ancestral step (``tg_step_epilogue_sigma``): ``coef`` = the scheduler's ``coef_table`` on the device, ``noise`` =
     the pre-drawn ancestral noise table [n_steps, n_img, C, h, w] (storage dtype or fp32) or None"""
-    n_img = latents.shape[0]
-    chw = latents[0].numel()
-    hw = latents.shape[-1] * latents.shape[-2]
-    mask_per_img = 1 if (frozen_mask is not None and frozen_mask.numel() == n_img * hw and n_img > 1) else 0
-    mi_dt = -1 if model_in is None else _SRC[model_in.dtype]
-    nz_dt = -1 if noise is None else _SRC[noise.dtype]
-    _lib.check(_lib.lib().tg_step_epilogue_sigma(_ptr(noise_pred), _ptr(latents), n_img, chw, hw, 1 if has_cfg else 0, float(guidance_scale),
-                                                 _ptr(coef), _ptr(step_idx), 1 if advance else 0, _ptr(noise), nz_dt, _ptr(frozen),
-                                                 _ptr(frozen_mask), mask_per_img, int(frozen_steps), _ptr(history), _ptr(model_in), mi_dt,
-                                                 _stream()))
+    _step_epilogue("tg_step_epilogue_sigma", noise_pred, latents, guidance_scale, coef, step_idx, has_cfg, advance, frozen, frozen_mask, frozen_steps,
+                   history, model_in, own=(_ptr(noise), -1 if noise is None else _SRC[noise.dtype]))
 
 
 def step_epilogue_dpm(noise_pred, latents, x0_prev, guidance_scale, coef, step_idx, *, has_cfg=True, advance=True, frozen=None,
                       frozen_mask=None, frozen_steps=0, history=None, model_in=None):
     """DPM-Solver++ multistep step (``tg_step_epilogue_dpm``): ``coef`` = ``DPMSolverMultistepScheduler.coef_table`` on the device
     (fp32 [n_steps, 8]), ``x0_prev`` = the fp32 state tensor shaped like ``latents`` (read when the row's C != 0, then overwritten)"""
-    n_img = latents.shape[0]
-    chw = latents[0].numel()
-    hw = latents.shape[-1] * latents.shape[-2]
     if x0_prev is None or x0_prev.dtype != torch.float32 or x0_prev.numel() != latents.numel() or not x0_prev.is_contiguous():
         raise ValueError("step_epilogue_dpm: x0_prev must be a contiguous fp32 tensor with the latents' element count")
     if coef.dtype != torch.float32 or coef.dim() != 2 or coef.shape[1] != 8 or not coef.is_contiguous():
         raise ValueError("step_epilogue_dpm: coef must be a contiguous fp32 [n_steps, 8] table")
-    mask_per_img = 1 if (frozen_mask is not None and frozen_mask.numel() == n_img * hw and n_img > 1) else 0
-    mi_dt = -1 if model_in is None else _SRC[model_in.dtype]
-    _lib.check(_lib.lib().tg_step_epilogue_dpm(_ptr(noise_pred), _ptr(latents), _ptr(x0_prev), n_img, chw, hw, 1 if has_cfg else 0,
-                                               float(guidance_scale), _ptr(coef), _ptr(step_idx), 1 if advance else 0, _ptr(frozen),
-                                               _ptr(frozen_mask), mask_per_img, int(frozen_steps), _ptr(history), _ptr(model_in), mi_dt,
-                                               _stream()))
+    _step_epilogue("tg_step_epilogue_dpm", noise_pred, latents, guidance_scale, coef, step_idx, has_cfg, advance, frozen, frozen_mask, frozen_steps,
+                   history, model_in, state=(_ptr(x0_prev),))
 
 
 def pixel_unshuffle(x, factor):

@@ -12,6 +12,7 @@ dimension (CFG batch 2*n: all uncond rows first, then all cond rows = ``noise_pr
 """
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 
@@ -50,6 +51,33 @@ def prepare_ip_embeds(prompt_embeds, negative_prompt_embeds, image_prompt_embeds
 _engine_ids = iter(range(1, 1 << 30))
 
 
+# What the engine has to know about a sampler, resolved once per engine from the scheduler's class: the dtype of the walked timestep list, the extra
+# device state its step keeps ("x0_prev": fp32 like the latents; "step_noise": [steps, n_img, C, h, w] in the model dtype; None), whether the model
+# input is scaled (step 0 by ``in_div0`` in ``_reset``, the later ones by the epilogue) and the step-epilogue launch, called as
+# ``epilogue(engine, noise_pred, **the frozen / history / model_in arguments every epilogue takes)``.
+_Sampler = namedtuple("_Sampler", "kind t_dtype state scales_input epilogue")
+
+
+def _ddim_epilogue(e, noise_pred, **kw):
+    ops.step_epilogue(noise_pred, e.latents, e.g, e.coef, e.step_idx, prediction_type=e.pred_type, **kw)
+
+
+def _sigma_epilogue(e, noise_pred, **kw):
+    ops.step_epilogue_sigma(noise_pred, e.latents, e.g, e.coef, e.step_idx, noise=e.step_noise, **kw)
+
+
+def _dpm_epilogue(e, noise_pred, **kw):
+    ops.step_epilogue_dpm(noise_pred, e.latents, e.x0_prev, e.g, e.coef, e.step_idx, **kw)
+
+
+# DDIM: the reference's own update; Euler / Euler ancestral (the SDXL flow): sigma-parameterised update, tg_step_epilogue_sigma; DPM-Solver++
+# multistep (opt-in, models/models.py:36-37): tg_step_epilogue_dpm with one extra state tensor.  The first class the scheduler is an instance of wins.
+_SAMPLERS = ((EulerAncestralDiscreteScheduler, _Sampler("euler_a", torch.float32, "step_noise", True, _sigma_epilogue)),
+             (EulerDiscreteScheduler, _Sampler("euler", torch.float32, None, True, _sigma_epilogue)),
+             (DPMSolverMultistepScheduler, _Sampler("dpm", torch.int64, "x0_prev", False, _dpm_epilogue)),
+             (DDIMScheduler, _Sampler("ddim", torch.int64, None, False, _ddim_epilogue)))
+
+
 class DenoiseEngine:
     """Batched CFG denoiser for ``n_img`` independent character images on one GPU.
 
@@ -76,19 +104,13 @@ class DenoiseEngine:
         dev, dt, cfg = unet.device, unet.dtype, unet.config
         self.dev, self.dt = dev, dt
         C = cfg.in_channels
-        # DDIM: the reference's own update; Euler / Euler ancestral (the SDXL flow): sigma-parameterised update, tg_step_epilogue_sigma;
-        # DPM-Solver++ multistep (opt-in, models/models.py:36-37): tg_step_epilogue_dpm with one extra state tensor
-        self.kind = ("euler_a" if isinstance(self.scheduler, EulerAncestralDiscreteScheduler) else
-                     "euler" if isinstance(self.scheduler, EulerDiscreteScheduler) else
-                     "dpm" if isinstance(self.scheduler, DPMSolverMultistepScheduler) else
-                     "ddim" if isinstance(self.scheduler, DDIMScheduler) else None)
-        if self.kind is None:
+        self.sampler = next((rec for cls, rec in _SAMPLERS if isinstance(self.scheduler, cls)), None)
+        if self.sampler is None:
             raise TypeError(f"DenoiseEngine: unsupported scheduler {type(self.scheduler).__name__}; the step epilogues exist for theatergen_amd.scheduler."
                             "DDIMScheduler, EulerDiscreteScheduler, EulerAncestralDiscreteScheduler and DPMSolverMultistepScheduler")
-        self.sigma_kind = self.kind in ("euler", "euler_a")
+        self.kind = self.sampler.kind
         self.scheduler.set_timesteps(num_inference_steps)
-        tdt = torch.float32 if self.sigma_kind else torch.int64
-        self.timesteps = self.scheduler.timesteps.clone() if timesteps is None else torch.as_tensor(timesteps, dtype=tdt).clone()
+        self.timesteps = self.scheduler.timesteps.clone() if timesteps is None else torch.as_tensor(timesteps, dtype=self.sampler.t_dtype).clone()
         num_inference_steps = self.steps = int(self.timesteps.numel())
         self.t_table = self.timesteps.to(device=dev, dtype=torch.float32)
         self.coef = self.scheduler.coef_table(self.timesteps).to(dev)
@@ -113,17 +135,14 @@ class DenoiseEngine:
         self._tproj_table = None
         self._tproj_key = None
         self.adapter_feats = None      # T2I-Adapter features: static CFG-duplicated token-major buffers (set_adapter)
-        self.step_noise = None         # Euler ancestral: the per-step noise table (set_step_noise)
+        # Euler ancestral: the per-step noise table (set_step_noise)
+        self.step_noise = torch.zeros((self.steps, n_img, C, self.h, self.w), dtype=dt, device=dev) if self.sampler.state == "step_noise" else None
         self._noise_set = False
-        self.x0_prev = None
-        if self.kind == "dpm":
-            # the multistep state: allocated once (a captured graph holds its address); _reset leaves it alone, row 0 never reads it
-            self.x0_prev = torch.zeros_like(self.latents)
-        if self.sigma_kind:
-            # scale_model_input of step 0 (the epilogue writes the later ones): x / sqrt(sigma_0^2 + 1)
-            self.in_div0 = float(self.scheduler.model_input_divisor(self.scheduler.index_for_timestep(self.timesteps[0], self.timesteps)))
-        if self.kind == "euler_a":
-            self.step_noise = torch.zeros((num_inference_steps, n_img, C, self.h, self.w), dtype=dt, device=dev)
+        # DPM: the multistep state, allocated once (a captured graph holds its address); _reset leaves it alone, row 0 never reads it
+        self.x0_prev = torch.zeros_like(self.latents) if self.sampler.state == "x0_prev" else None
+        # scale_model_input of step 0 (the epilogue writes the later ones): x / sqrt(sigma_0^2 + 1); None where the sampler does not scale
+        self.in_div0 = (float(self.scheduler.model_input_divisor(self.scheduler.index_for_timestep(self.timesteps[0], self.timesteps)))
+                        if self.sampler.scales_input else None)
 
     # ---- conditioning -----------------------------------------------------------------------------------
     def set_conditioning(self, encoder_hidden_states, added_cond_kwargs=None):
@@ -253,19 +272,8 @@ class DenoiseEngine:
         noise_pred = self.unet(self.model_in, self.sched, self.enc, added_cond_kwargs=self.added, return_dict=False,
                                out_dtype=torch.float32, down_block_additional_residuals=down,
                                mid_block_additional_residual=mid, time_proj=tp, shared_pair=self.added is None)[0]
-        if self.kind == "dpm":
-            ops.step_epilogue_dpm(noise_pred, self.latents, self.x0_prev, self.g, self.coef, self.step_idx, advance=True, frozen=self.frozen,
-                                  frozen_mask=self.frozen_mask, frozen_steps=self.frozen_steps, history=self.history, model_in=self.model_in)
-            return
-        if self.sigma_kind:
-            ops.step_epilogue_sigma(noise_pred, self.latents, self.g, self.coef, self.step_idx, advance=True, noise=self.step_noise,
-                                    frozen=self.frozen, frozen_mask=self.frozen_mask, frozen_steps=self.frozen_steps, history=self.history,
-                                    model_in=self.model_in)
-            return
-        ops.step_epilogue(noise_pred, self.latents, self.g, self.coef, self.step_idx, advance=True,
-                          prediction_type=self.pred_type, frozen=self.frozen,
-                          frozen_mask=self.frozen_mask, frozen_steps=self.frozen_steps, history=self.history,
-                          model_in=self.model_in)
+        self.sampler.epilogue(self, noise_pred, advance=True, frozen=self.frozen, frozen_mask=self.frozen_mask, frozen_steps=self.frozen_steps,
+                              history=self.history, model_in=self.model_in)
 
     def _signature(self):
         """Launch constants baked into a captured graph: the frozen-mask configuration and the guidance scale.  The IP scales
@@ -277,14 +285,9 @@ class DenoiseEngine:
     def _reset(self, latents):
         self.latents.copy_(latents.to(device=self.dev, dtype=torch.float32))
         self.history[0].copy_(self.latents)
-        if self.sigma_kind:
-            x0 = self.latents / self.in_div0                      # scale_model_input of step 0, then the `.half()`
-            self.model_in[:self.n_img].copy_(x0)
-            self.model_in[self.n_img:].copy_(x0)
-            self.step_idx.zero_()
-            return
-        self.model_in[:self.n_img].copy_(self.latents)           # dtype cast on copy = the `.half()` of pipelines.py:414
-        self.model_in[self.n_img:].copy_(self.latents)
+        x0 = self.latents if self.in_div0 is None else self.latents / self.in_div0     # scale_model_input of step 0
+        self.model_in[:self.n_img].copy_(x0)                     # dtype cast on copy = the `.half()` of pipelines.py:414
+        self.model_in[self.n_img:].copy_(x0)
         self.step_idx.zero_()
 
     def _capture(self):

@@ -18,6 +18,15 @@ import torch
 from . import ops
 
 
+def _device_step(launch, model_output, sample, return_dict):
+    """The tail every ``step()`` here shares: fp32 contiguous copies, ``launch(model_output, out)`` updates ``out`` in place on the GPU, the result goes
+    back to the sample's dtype as ``.prev_sample`` (or a 1-tuple)."""
+    out = sample.detach().to(torch.float32).clone(memory_format=torch.contiguous_format)
+    launch(model_output.detach().to(torch.float32).contiguous(), out)
+    out = out.to(sample.dtype)
+    return SimpleNamespace(prev_sample=out) if return_dict else (out,)
+
+
 class DDIMScheduler:
     order = 1
 
@@ -84,13 +93,9 @@ class DDIMScheduler:
             coef = torch.stack([a_t ** 0.5, (1 - a_t) ** 0.5, a_prev ** 0.5, (1 - a_prev) ** 0.5]).reshape(1, 4)
             self._coef_cache[key] = (coef.to(dev, torch.float32), torch.zeros(1, dtype=torch.int32, device=dev))
         coef, idx = self._coef_cache[key]
-        out = sample.detach().to(torch.float32).clone()
-        ops.step_epilogue(model_output.to(torch.float32).contiguous(), out, 0.0, coef, idx, has_cfg=False, advance=False,
-                          prediction_type=0 if self.config.prediction_type == "epsilon" else 1)
-        out = out.to(sample.dtype)
-        if not return_dict:
-            return (out,)
-        return SimpleNamespace(prev_sample=out)
+        pred = 0 if self.config.prediction_type == "epsilon" else 1
+        return _device_step(lambda m, out: ops.step_epilogue(m, out, 0.0, coef, idx, has_cfg=False, advance=False, prediction_type=pred),
+                            model_output, sample, return_dict)
 
     def add_noise_coeffs(self, timesteps):
         a = self.alphas_cumprod[timesteps]
@@ -235,13 +240,10 @@ class _SigmaScheduler:
         ce, su = self._update(k)
         coef = torch.stack([ce, su, torch.ones(()), self.sigmas[k]]).reshape(1, 4).to(dev, torch.float32)
         noise = torch.randn(model_output.shape, dtype=model_output.dtype, device=dev, generator=generator) if (self.ancestral or generator is not None) else None
-        out = sample.detach().to(torch.float32).clone()
-        ops.step_epilogue_sigma(model_output.to(torch.float32).contiguous(), out, 0.0, coef, torch.zeros(1, dtype=torch.int32, device=dev),
-                                has_cfg=False, advance=False, noise=noise.contiguous() if self.ancestral else None)
-        out = out.to(sample.dtype)
-        if not return_dict:
-            return (out,)
-        return SimpleNamespace(prev_sample=out)
+        idx = torch.zeros(1, dtype=torch.int32, device=dev)
+        return _device_step(lambda m, out: ops.step_epilogue_sigma(m, out, 0.0, coef, idx, has_cfg=False, advance=False,
+                                                                   noise=noise.contiguous() if self.ancestral else None),
+                            model_output, sample, return_dict)
 
     def add_noise(self, original_samples, noise, timesteps):
         """``x0 + sigma(t) * noise`` broadcast over a vector of timesteps (sigma looked up by the position of t in ``self.timesteps``): one
@@ -441,15 +443,12 @@ class DPMSolverMultistepScheduler:
             if self._taken:
                 raise ValueError(f"{type(self).__name__}.step: the sample changed shape or device inside a chain")
             self._x0_prev = torch.empty(sample.shape, dtype=torch.float32, device=dev)
-        out = sample.detach().to(torch.float32).clone(memory_format=torch.contiguous_format)
-        ops.step_epilogue_dpm(model_output.detach().to(torch.float32).contiguous(), out, self._x0_prev, 0.0, table if self._taken else first,
-                              index[i:i + 1], has_cfg=False, advance=False)
+        res = _device_step(lambda m, out: ops.step_epilogue_dpm(m, out, self._x0_prev, 0.0, table if self._taken else first, index[i:i + 1],
+                                                                has_cfg=False, advance=False),
+                           model_output, sample, return_dict)
         self._taken += 1
         self._last_index = i
-        out = out.to(sample.dtype)
-        if not return_dict:
-            return (out,)
-        return SimpleNamespace(prev_sample=out)
+        return res
 
     add_noise_coeffs = DDIMScheduler.add_noise_coeffs
     add_noise = DDIMScheduler.add_noise          # sqrt(a_t) x0 + sqrt(1 - a_t) noise: the same forward process, one shared implementation

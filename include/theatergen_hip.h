@@ -614,7 +614,10 @@ int tg_rc_kv_pack(int32_t dtype, int32_t batch, const void* k, const void* vt, i
  * `wpo` != NULL also Transformer2DModel.proj_out + its residual (models/transformer_2d.py:316-327), in one launch:
  *     h3 = net2(a * gelu(g)) + b2 + h,  [a | g] = proj(LayerNorm(h)) + b1;      out = wpo ? proj_out(h3) + b + res0 : h3
  * `w1` / `w2` / `b2`: theatergen_amd/rowchain.py::pack_ff (LayerNorm gamma / beta folded into proj; the kernel normalises the rows);
- * `wpo`: rc_pack_tiles stream of proj_out (+ bias).  `inner` = the hidden width (1280).  `dbg`: dev timing switches, 0. */
+ * `wpo`: rc_pack_tiles stream of proj_out (+ bias).  `inner` = the hidden width (1280).  `dbg`: dev timing switches in the low 16 bits, 0;
+ * TG_RC_FF_TWO_WAVE selects the kernel that runs two waves per SIMD (one 8-wave workgroup per 128 tokens, 16 tokens per wave on 16x16x32 MFMAs):
+ * `w1` / `w2` are then rowchain.py::pack_ff2 streams and `wpo` a pack_po2 stream (other fragment order, same sizes). */
+#define TG_RC_FF_TWO_WAVE 0x10000
 typedef struct {
   int32_t dtype;
   const void* h; int64_t ldh;

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("THEATERGEN_HIP_LIB") or os.path.join(HERE, "lib", "li
 TG_BF16, TG_F16 = 0, 1
 ABI_VERSION = 308          # TG_ABI_VERSION of include/theatergen_hip.h this binding was written against
 ACT_NONE, ACT_SILU, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2, 3
+RC_FF_TWO_WAVE = 0x10000     # TG_RC_FF_TWO_WAVE: kernel selector bit in the `dbg` word of tg_rc_ff_desc
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 

@@ -140,6 +140,7 @@ HOT_GATES = [
     # row-chain kernels (round 4): straight-line register-array code — any scratch means an array fell out of the registers
     ("rc_xattn_kernel<", 0, 256),
     ("rc_ff_kernel<", 0, 256),
+    ("rc_ff2_kernel<", 0, 256),                                    # two waves per SIMD: a 257th register would halve the occupancy the kernel exists for
     ("rc_front_kernel<", 0, 216),                                  # round 4's first version spilled 108 registers (30 % of its launch)
     ("rc_linear_kernel<", 0, 256),                                 # every instance (the UNet launches <T,20,8,2,false,0>, plain / + residual)
     ("skinny_gemm_kernel<", 0, 256),                               # round 5: the CK = 16 / 20 instances spilled 44 .. 164 bytes

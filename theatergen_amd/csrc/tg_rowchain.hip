@@ -1090,10 +1090,10 @@ template <int N, typename V8> __device__ __forceinline__ void lds_wait3(V8& f0, 
 struct RcFfParams {
   const void* h;        // [M, 320] the stream before norm3 (= the residual)
   long ldh;
-  const void* w1;       // rowchain.pack_ff: n_slices x 41 KiB (+ 3 KiB pad)
-  const void* w2;       // n_slices x 20 KiB
+  const void* w1;       // rowchain.pack_ff (rc_ff_kernel) / pack_ff2 (rc_ff2_kernel): n_slices x 41 KiB (+ 3 KiB pad)
+  const void* w2;       // n_slices x 20 KiB, of the same pack function
   const float* b2;      // fp32 [320]
-  const void* wpo;      // proj_out as rc_pack_tiles stream, or NULL (then `out` = h3)
+  const void* wpo;      // proj_out as rc_pack_tiles stream (rc_ff_kernel) / rowchain.pack_po2 stream (rc_ff2_kernel), or NULL (then `out` = h3)
   const void* res0;     // [M, 320] residual of proj_out
   long ldres;
   void* out;
@@ -1101,7 +1101,8 @@ struct RcFfParams {
   long M;
   int n_slices;         // inner / 32, even, >= 2
   float ln_eps;
-  int dbg;              // dev timing switches: 1 no proj MFMAs, 2 no GEGLU arithmetic, 4 no net.2 MFMAs
+  int dbg;              // dev timing switches: 1 no proj MFMAs, 2 no GEGLU arithmetic, 4 no net.2 MFMAs (the descriptor's TG_RC_FF_TWO_WAVE selector bit is
+                        // masked out by the C entry: it chooses the kernel on the host and never reaches one)
 };
 
 template <typename T, bool PROJ, int DBG = 0>
@@ -1439,22 +1440,342 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// rc_ff2_kernel: the chain of rc_ff_kernel at TWO waves per SIMD.  rc_ff_kernel's single wave per SIMD runs its interleaved stream at the SUM of its
+// MFMA and VALU issue times (profiles/r4_rowchain_findings.md) and every workgroup sits in its row-load / store phases with nothing else on the SIMD.
+// Here ONE 8-wave workgroup per CU shares one weight stream (same LDS stages, same 128 tokens per stream: the L2 -> LDS traffic does not change), and a
+// wave owns 16 tokens on v_mfma_f32_16x16x32: 80 net.2 accumulator registers (20 tiles of 16 channels), two projection slots of 16, the normalised rows
+// as 10 B pieces of 32 channels — within 256 registers.  Index maps (n = lane & 15 the token, g = lane >> 4, e = element of a 16-byte piece):
+//   rows as B operand, k-step s                 lane (n, g) element e = channel 32 s + 8 g + e                    (16 contiguous bytes of the row)
+//   proj tile (value / gate, u) of slice j      MFMA row r = hidden channel 32 j + 16 u + r; accumulator register i of lane group g = row 4 g + i
+//   hidden piece of slice j (net.2's B operand) element e = [u = e >> 2][i = e & 3] = hidden channel 32 j + 16 (e >> 2) + 4 g + (e & 3)
+//   net.2 / proj_out tile t = 2 s + u           MFMA row r = output channel 32 s + 8 (r >> 2) + 4 u + (r & 3): registers i of tiles 2 s, 2 s + 1 of lane
+//                                               group g ARE elements 0..3, 4..7 of the rows' B piece s (the residual, proj_out's operand, the store)
+// Streams: rowchain.pack_ff2 / pack_po2 (same byte sizes per slice / stage as pack_ff / rc_pack_tiles, fragments in the order above; fragment
+// k = 2 s + u so that consecutive MFMAs of one kind alternate between two accumulators).  The pipeline is rc_ff_kernel's: iteration j issues proj(j),
+// GEGLU(j - 1) in micro-steps between the MFMAs, net.2(j - 2); asm fragment reads with counted lgkmcnt waits.
+template <typename T, bool PROJ>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void rc_ff2_kernel(RcFfParams p) {
+  typedef typename Vec<T>::v8 V8;
+  constexpr int KS = 10, NW = 8;
+  constexpr int W1B = 41 * 1024, W1SLOT = 44 * 1024, W2B = 20 * 1024;
+  constexpr int W2OFF = 2 * W1SLOT;
+  constexpr int TBW = 21 * 1024, SLOT = 24 * 1024;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = lane & 15, g = lane >> 4;
+  const int lbid = rc_block_id((int)blockIdx.x, (int)gridDim.x);
+  const long tok = ((long)lbid * NW + wave) * 16 + n;
+  const bool ok = tok < p.M;
+  const long row = ok ? tok : p.M - 1;
+  const int NS = p.n_slices;
+  const char* w1g = reinterpret_cast<const char*>(p.w1) + lane * 16 + wave * 1024;
+  const char* w2g = reinterpret_cast<const char*>(p.w2) + lane * 16 + wave * 1024;
+  auto issue_w1 = [&](int j) __attribute__((always_inline)) {      // slice j -> proj slot j & 1: 44 KiB-pieces over 8 waves (41 KiB + 3 KiB of the next slice / the pad)
+    const char* s0 = w1g + (long)j * W1B;
+    char* dst = smem + (j & 1) * W1SLOT + wave * 1024;
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+      if (q < 5 || wave < 4)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(s0 + q * NW * 1024),
+                                         (__attribute__((address_space(3))) void*)(dst + q * NW * 1024), 16, 0, 0);
+  };
+  auto issue_w2 = [&](int j) __attribute__((always_inline)) {      // slice j -> net.2 slot j & 1: 20 KiB-pieces over 8 waves
+    const char* s0 = w2g + (long)j * W2B;
+    char* dst = smem + W2OFF + (j & 1) * W2B + wave * 1024;
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+      if (q < 2 || wave < 4)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(s0 + q * NW * 1024),
+                                         (__attribute__((address_space(3))) void*)(dst + q * NW * 1024), 16, 0, 0);
+  };
+  issue_w1(0);
+
+  // the wave's 16 rows -> normalised B pieces (what norm3 hands to the feed-forward); the rows themselves are read again for the residual
+  V8 HN[KS];
+  {
+    V8 H[KS];
+    const T* xp = reinterpret_cast<const T*>(p.h) + row * p.ldh + 8 * g;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) H[s] = *reinterpret_cast<const V8*>(xp + 32 * s);
+    float sum = 0.f;
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sum += to_f32<T>(H[s][e]);
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    const float mean = sum * (1.0f / 320.0f);
+    float c2 = 0.f;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      asm volatile("" : "+v"(H[s]));
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { const float d = to_f32<T>(H[s][e]) - mean; c2 = __builtin_fmaf(d, d, c2); }
+    }
+    c2 += __shfl_xor(c2, 16, 64);
+    c2 += __shfl_xor(c2, 32, 64);
+    const float rstd = __builtin_amdgcn_rsqf(c2 * (1.0f / 320.0f) + p.ln_eps);
+    const float nm = -mean * rstd;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      asm volatile("" : "+v"(H[s]));
+      float f[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[e] = __builtin_fmaf(to_f32<T>(H[s][e]), rstd, nm);
+      HN[s] = pack8<T>(f);
+    }
+  }
+  // net.2's accumulators for the whole kernel: tile t = 2 s + u, register i <-> channel 32 s + 8 g + 4 u + i; seeded with b2
+  f32x4 out[20];
+#pragma unroll
+  for (int t = 0; t < 20; ++t) out[t] = *reinterpret_cast<const f32x4*>(p.b2 + 32 * (t >> 1) + 8 * g + 4 * (t & 1));
+
+  f32x4 acc_a[2][2], acc_g[2][2];
+  V8 hid[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) hid[q][e] = from_f32<T>(0.f);
+
+  // one pipeline iteration: proj(j) [F1], GEGLU(j - 1) [GG], net.2(j - 2) [F2]; PAR = j & 1 selects slots / accumulator sets
+  auto iteration = [&](int j, auto par_c, auto f1_c, auto gg_c, auto f2_c) __attribute__((always_inline)) {
+    constexpr int PAR = decltype(par_c)::value;
+    constexpr bool F1 = decltype(f1_c)::value, GG = decltype(gg_c)::value, F2 = decltype(f2_c)::value;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (j + 1 < NS) issue_w1(j + 1);
+    if (j >= 1 && j - 1 < NS) issue_w2(j - 1);
+    // slot x = 3 k + {0: value fragment k, 1: gate fragment k, 2: net.2 tile k}, k = 2 s + u for the projections; the fragment of slot x is read
+    // LA slots ahead of its MFMA (asm reads, counted waits: see lds_read16)
+    constexpr int LA = 9;
+    const unsigned lbase = (unsigned)reinterpret_cast<size_t>((__attribute__((address_space(3))) char*)smem);
+    const unsigned a1 = lbase + PAR * W1SLOT + lane * 16, a2 = lbase + W2OFF + PAR * W2B + lane * 16;
+    V8 fr[60];
+    auto rd = [&](auto xc) __attribute__((always_inline)) {
+      constexpr int x = decltype(xc)::value;
+      constexpr int k = x / 3, w = x % 3;
+      if constexpr (w == 0) { if constexpr (F1) lds_read16<k * 1024>(fr[x], a1); }
+      else if constexpr (w == 1) { if constexpr (F1) lds_read16<(20 + k) * 1024>(fr[x], a1); }
+      else { if constexpr (F2) lds_read16<k * 1024>(fr[x], a2); }
+    };
+    // the projection accumulators start from the slice's bias page (register i of lane group g <- bias[16 u + 4 g + i]): asm reads as well, IN FRONT of the
+    // fragment reads (LDS returns in order: they have landed with slot 0's fragment) — a plain load here costs an lgkmcnt(0) over the whole read-ahead
+    if constexpr (F1) {
+      const unsigned ap = lbase + PAR * W1SLOT + 40 * 1024 + g * 16;
+      lds_read16<0>(acc_a[PAR][0], ap);
+      lds_read16<64>(acc_a[PAR][1], ap);
+      lds_read16<128>(acc_g[PAR][0], ap);
+      lds_read16<192>(acc_g[PAR][1], ap);
+    }
+    static_for<LA>([&](auto xc) __attribute__((always_inline)) { rd(xc); });
+    // GEGLU micro-step state (one element in flight), rc_ff_kernel's arithmetic: gelu(g) = g (0.5 + 0.5 erf(g / sqrt 2)), erf(z) = z P(z^2) on |z| <= 3.
+    // 8 elements x 4 parts = 32 micro-steps spread over the 60 slots
+    float ge_z = 0.f, ge_t = 0.f, ge_p = 0.f;
+    float hv[8];
+    auto geglu_micro = [&](int mstep) __attribute__((always_inline)) {
+      const int e = mstep >> 2, part = mstep & 3;
+      const float a = acc_a[PAR ^ 1][e >> 2][e & 3], gt = acc_g[PAR ^ 1][e >> 2][e & 3];
+      if (part == 0) {
+        ge_z = __builtin_amdgcn_fmed3f(gt * 0.70710678118654752440f, -3.0f, 3.0f);
+        ge_t = ge_z * ge_z;
+      } else if (part == 1) {
+        float q = __builtin_fmaf(-4.0553346e-07f, ge_t, 1.7159753e-05f);
+        q = __builtin_fmaf(q, ge_t, -3.1459445e-04f);
+        q = __builtin_fmaf(q, ge_t, 3.3187051e-03f);
+        ge_p = __builtin_fmaf(q, ge_t, -2.2685785e-02f);
+      } else if (part == 2) {
+        float q = __builtin_fmaf(ge_p, ge_t, 1.0771781e-01f);
+        q = __builtin_fmaf(q, ge_t, -3.7323141e-01f);
+        q = __builtin_fmaf(q, ge_t, 1.1278958f);
+        ge_p = q * ge_z;                                     // erf(g / sqrt 2)
+      } else {
+        hv[e] = a * gt * __builtin_fmaf(0.5f, ge_p, 0.5f);
+        if (e == 7) hid[PAR ^ 1] = pack8<T>(hv);
+      }
+    };
+    __builtin_amdgcn_sched_barrier(0);
+    static_for<60>([&](auto xc) __attribute__((always_inline)) {
+      constexpr int x = decltype(xc)::value;
+      constexpr int k = x / 3, w = x % 3;
+      constexpr bool act = (w == 2) ? F2 : F1;
+      if constexpr (F1 && F2) {
+        if constexpr (w == 0) {      // the three reads of the group LA slots ahead, in one go
+          if constexpr (x + LA < 60) rd(std::integral_constant<int, (x + LA < 60 ? x + LA : 59)>{});
+          if constexpr (x + LA + 1 < 60) rd(std::integral_constant<int, (x + LA + 1 < 60 ? x + LA + 1 : 59)>{});
+          if constexpr (x + LA + 2 < 60) rd(std::integral_constant<int, (x + LA + 2 < 60 ? x + LA + 2 : 59)>{});
+        }
+      } else {
+        if constexpr (x + LA < 60) rd(std::integral_constant<int, (x + LA < 60 ? x + LA : 59)>{});
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (act) {
+        // reads issued after this slot's: the active slots in (x, min(59, x + LA)]
+        constexpr int hi_x = x + LA < 60 ? x + LA : 59;
+        constexpr int n_f1 = ((hi_x / 3) * 2 + (hi_x % 3 >= 1 ? 2 : 1)) - ((x / 3) * 2 + (x % 3 >= 1 ? 2 : 1));
+        constexpr int n_f2 = (hi_x + 1) / 3 - (x + 1) / 3;
+        constexpr int younger = (F1 ? n_f1 : 0) + (F2 ? n_f2 : 0);
+        if constexpr (F1 && F2) {
+          // steady state: one wait per slot group (value, gate, net.2 fragments of k): counted for the group's LAST fragment
+          if constexpr (w == 0) {
+            constexpr int hi3 = x + 2 + LA < 60 ? x + 2 + LA : 59;
+            lds_wait3<(hi3 - (x + 2) > 15 ? 15 : hi3 - (x + 2))>(fr[x], fr[x + 1], fr[x + 2]);
+          }
+        } else {
+          lds_wait<(younger > 15 ? 15 : younger)>(fr[x]);
+        }
+        if constexpr (F1 && x == 0) asm volatile("" : "+v"(acc_a[PAR][0]), "+v"(acc_a[PAR][1]), "+v"(acc_g[PAR][0]), "+v"(acc_g[PAR][1]));
+        if constexpr (w == 0) acc_a[PAR][k & 1] = mfma16(fr[x], HN[k >> 1], acc_a[PAR][k & 1]);
+        else if constexpr (w == 1) acc_g[PAR][k & 1] = mfma16(fr[x], HN[k >> 1], acc_g[PAR][k & 1]);
+        else out[k] = mfma16(fr[x], hid[PAR], out[k]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (GG) {
+        constexpr int m0 = 32 * x / 60, m1 = 32 * (x + 1) / 60;     // 0 or 1 micro-steps per slot
+        if constexpr (m1 > m0) {
+          geglu_micro(m0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    });
+    // anchor (see rc_ff_kernel): without a use HERE the compiler sinks this iteration's GEGLU arithmetic into the next iteration's block
+    if constexpr (GG) asm volatile("" :: "v"(hid[PAR ^ 1]));
+  };
+  using C0 = std::integral_constant<int, 0>;
+  using C1 = std::integral_constant<int, 1>;
+  using Tt = std::true_type;
+  using Ff = std::false_type;
+  iteration(0, C0{}, Tt{}, Ff{}, Ff{});
+  iteration(1, C1{}, Tt{}, Tt{}, Ff{});
+  for (int j = 2; j < NS; j += 2) {
+    iteration(j, C0{}, Tt{}, Tt{}, Tt{});
+    iteration(j + 1, C1{}, Tt{}, Tt{}, Tt{});
+  }
+  iteration(NS, C0{}, Ff{}, Tt{}, Tt{});
+  iteration(NS + 1, C1{}, Ff{}, Ff{}, Tt{});
+
+  // h3 = net.2 + b2 + h: the rows are read again (L2 / Infinity Cache); their B piece s IS the register layout of tiles 2 s, 2 s + 1
+  {
+    const T* hb = reinterpret_cast<const T*>(p.h);
+    asm volatile("" : "+s"(hb));
+    const T* xp = hb + row * p.ldh + 8 * g;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const V8 hr = gld<V8>(xp + 32 * s);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) out[2 * s + (e >> 2)][e & 3] += to_f32<T>(hr[e]);
+    }
+  }
+  auto pack_rows = [&](int s) __attribute__((always_inline)) {
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = out[2 * s + (e >> 2)][e & 3];
+    return pack8<T>(f);
+  };
+
+  T* outp = reinterpret_cast<T*>(p.out);
+  if constexpr (!PROJ) {
+    asm volatile("" : "+s"(outp));
+    T* op = outp + row * p.ldc + 8 * g;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const V8 pc = pack_rows(s);
+      if (ok) gst<V8>(op + 32 * s, pc);
+    }
+  } else {
+    // proj_out over the rounded h3 rows: 10 stages of 32 output channels (20 fragments + the bias page = 21 KiB) in a ring of three 24-KiB slots (the
+    // feed-forward slots are dead behind this barrier); every wave moves 3 KiB of a stage
+    V8 HB[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) HB[s] = pack_rows(s);
+    const char* wpg = reinterpret_cast<const char*>(p.wpo) + lane * 16 + wave * 1024;
+    auto issue_po = [&](int st) __attribute__((always_inline)) {
+      if (st >= 10) return;
+      const char* s0 = wpg + (long)st * TBW;
+      char* dst = smem + (st % 3) * SLOT + wave * 1024;
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(s0 + q * NW * 1024),
+                                         (__attribute__((address_space(3))) void*)(dst + q * NW * 1024), 16, 0, 0);
+    };
+    __builtin_amdgcn_s_barrier();
+    issue_po(0);
+    issue_po(1);
+    const T* rp = reinterpret_cast<const T*>(p.res0);
+    asm volatile("" : "+s"(rp), "+s"(outp));
+    rp += row * p.ldres + 8 * g;
+    T* op = outp + row * p.ldc + 8 * g;
+    const unsigned pbase = (unsigned)reinterpret_cast<size_t>((__attribute__((address_space(3))) char*)smem) + lane * 16;
+#pragma unroll
+    for (int st = 0; st < 10; ++st) {
+      // stage st has landed when at most `younger` vector-memory operations are outstanding.  Counted are only the operations EVERY wave issues behind
+      // the stage's three pieces — later stages' pieces and the residual loads (clamped rows: unconditional); the stores are predicated and may be
+      // absent, so they are not counted (when present the wait is slightly early, never late).
+      //   order: P0 P1 | st 0: L0 P2 (S0) | st 1: L1 P3 (S1) | ...   behind P(st): L(st - 1), P(st + 1)
+      if (st == 0) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+      else if (st == 9) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      // the residual piece as an asm load with its own counted wait (behind it: the three pieces of stage st + 2): hipcc's wait for a load that sits between
+      // LDS-DMA issues is vmcnt(0), which would end every stage on the round trip of the prefetch it has just issued
+      V8 r8;
+      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r8) : "v"(rp + 32 * st) : "memory");
+      issue_po(st + 2);
+      // fragments and the bias page by asm reads with counted waits (see lds_read16; a plain LDS load behind the stage's LDS-DMA issue makes hipcc wait
+      // vmcnt(0) in front of it: the prefetch would not be one)
+      const unsigned cb = pbase + (st % 3) * SLOT;
+      constexpr int PD = 8;
+      V8 a[20];
+      f32x4 acc[2];
+      lds_read16<20 * 1024>(acc[0], cb - lane * 16 + g * 16);
+      lds_read16<20 * 1024 + 64>(acc[1], cb - lane * 16 + g * 16);
+      static_for<PD>([&](auto xc) __attribute__((always_inline)) { constexpr int x = decltype(xc)::value; lds_read16<x * 1024>(a[x], cb); });
+      __builtin_amdgcn_sched_barrier(0);
+      static_for<20>([&](auto xc) __attribute__((always_inline)) {
+        constexpr int x = decltype(xc)::value;
+        if constexpr (x + PD < 20) lds_read16<(x + PD < 20 ? x + PD : 0) * 1024>(a[x + PD < 20 ? x + PD : 0], cb);
+        lds_wait<(x + PD < 20 ? PD : 19 - x)>(a[x]);
+        if constexpr (x == 0) asm volatile("" : "+v"(acc[0]), "+v"(acc[1]));
+        __builtin_amdgcn_sched_barrier(0);
+        acc[x & 1] = mfma16(a[x], HB[x >> 1], acc[x & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+      });
+      if (st + 2 < 10) asm volatile("s_waitcnt vmcnt(3)" : "+v"(r8));
+      else asm volatile("s_waitcnt vmcnt(0)" : "+v"(r8));
+      float o[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = acc[e >> 2][e & 3] + to_f32<T>(r8[e]);
+      const V8 pc = pack8<T>(o);
+      if (ok) gst<V8>(op + 32 * st, pc);
+    }
+  }
+}
+
+// one instantiation, hence one `static` attribute call, per KERNEL (the four kernels share the type void (*)(RcFfParams): a helper taking the kernel as
+// a function argument would set the dynamic-LDS attribute for the first one launched only)
+template <void (*K)(RcFfParams)>
+void launch_rc_ff_kernel(long grid, int threads, size_t lds, hipStream_t st, const RcFfParams& p) {
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)attr;
+  hipLaunchKernelGGL(K, dim3((unsigned)grid), dim3(threads), lds, st, p);
+}
+
 template <typename T>
 int launch_rc_ff(const tg_rc_ff_desc* d, const RcFfParams& p, hipStream_t st) {
   const size_t lds = 2 * 44 * 1024 + 2 * 20 * 1024;
   const long grid = (d->M + 127) / 128;
   // (the DBG instantiations of rc_ff_kernel — parts of the steady-state stream compiled out — were dev timing aids: numbers in
   // profiles/r4_rowchain_findings.md)
+  const bool two = (d->dbg & TG_RC_FF_TWO_WAVE) != 0;      // streams of pack_ff2 / pack_po2
   if (d->wpo != nullptr) {
-    auto k = rc_ff_kernel<T, true>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)attr;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, st, p);
+    if (two) launch_rc_ff_kernel<rc_ff2_kernel<T, true>>(grid, 512, lds, st, p);
+    else launch_rc_ff_kernel<rc_ff_kernel<T, true>>(grid, 256, lds, st, p);
   } else {
-    auto k = rc_ff_kernel<T, false>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)attr;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, st, p);
+    if (two) launch_rc_ff_kernel<rc_ff2_kernel<T, false>>(grid, 512, lds, st, p);
+    else launch_rc_ff_kernel<rc_ff_kernel<T, false>>(grid, 256, lds, st, p);
   }
   TG_LAUNCH_CHECK();
   return TG_OK;
@@ -1567,10 +1888,10 @@ extern "C" int tg_rc_ff(const tg_rc_ff_desc* d, void* stream) {
   TG_CHECK(d->inner >= 64 && d->inner % 64 == 0, TG_ERR_ARG, "tg_rc_ff: inner = %d must be a multiple of 64", d->inner);
   TG_CHECK(d->ldh >= 320 && d->ldh % 8 == 0 && d->ldc >= 320 && d->ldc % 8 == 0, TG_ERR_ARG, "tg_rc_ff: row pitches");
   TG_CHECK(!d->wpo || (d->res0 && d->ldres >= 320 && d->ldres % 8 == 0), TG_ERR_ARG, "tg_rc_ff: proj_out needs its residual");
-  TG_CHECK(d->dbg == 0 || rc_dev_enabled(), TG_ERR_ARG, "tg_rc_ff: dbg = %d (dev switches need TG_RC_DEV=1)", d->dbg);
+  TG_CHECK((d->dbg & ~TG_RC_FF_TWO_WAVE) == 0 || rc_dev_enabled(), TG_ERR_ARG, "tg_rc_ff: dbg = %d (dev switches need TG_RC_DEV=1)", d->dbg);
   RcFfParams p;
   p.h = d->h; p.ldh = d->ldh; p.w1 = d->w1; p.w2 = d->w2; p.b2 = d->b2; p.wpo = d->wpo; p.res0 = d->res0; p.ldres = d->ldres;
-  p.out = d->out; p.ldc = d->ldc; p.M = d->M; p.n_slices = d->inner / 32; p.ln_eps = d->ln_eps; p.dbg = d->dbg;
+  p.out = d->out; p.ldc = d->ldc; p.M = d->M; p.n_slices = d->inner / 32; p.ln_eps = d->ln_eps; p.dbg = d->dbg & ~TG_RC_FF_TWO_WAVE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (d->dtype == TG_BF16) return launch_rc_ff<bf16_t>(d, p, st);
   return launch_rc_ff<f16_t>(d, p, st);

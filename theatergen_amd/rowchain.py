@@ -14,8 +14,10 @@ from .weights_pack import rc_pack, rc_pack_tiles
 # TG_RC: 0 = the row-chain kernels are never selected (old-path A/B), 1 = default.  TG_RC_MIN_ROWS: below this many token rows the
 # LDS-tiled GEMMs / the three-launch cross-attention stay (a row-chain workgroup is a long serial chain: it needs a full chip of them)
 ENABLED = os.environ.get("TG_RC", "1") != "0"
-# dev A/B bits: 0 tg_rc_linear swaps (K = 320), 1 tg_rc_xattn, 2 tg_rc_ff, 3 tg_rc_front
-MODE = int(os.environ.get("TG_RC_MODE", "15"))
+# dev A/B bits: 0 tg_rc_linear swaps (K = 320), 1 tg_rc_xattn, 2 tg_rc_ff, 3 tg_rc_front, 5 tg_rc_ff on its two-waves-per-SIMD kernel
+# (rc_ff2_kernel, streams of pack_ff2 / pack_po2; without the bit: rc_ff_kernel, one wave per SIMD).  (Bit 4 was round 4's K = 640 kernel.)
+MODE = int(os.environ.get("TG_RC_MODE", "47"))
+FF_TWO_WAVE = ops._lib.RC_FF_TWO_WAVE          # TG_RC_FF_TWO_WAVE of include/theatergen_hip.h (``dbg`` word of tg_rc_ff_desc)
 MIN_ROWS = int(os.environ.get("TG_RC_MIN_ROWS", "8192"))
 # rc_linear / rc_front / rc_ff are one long serial chain per workgroup (a lone rc_ff workgroup needs ~95 us): below one full round of 128-token
 # workgroups (256 CUs x 128 rows) the LDS-tiled launches are as fast or faster (8192 rows: rc_ff 95 us vs 64 us, rc_front 51 + 16 vs 59 us)
@@ -175,3 +177,65 @@ def pack_ff(w1, b1, gamma, beta, w2, b2):
     s2 = f2.reshape(-1).view(torch.uint8)
     bb2 = (b2.detach().float() if b2 is not None else torch.zeros(C, device=dev)).contiguous()
     return s1.contiguous(), s2.contiguous(), bb2
+
+
+# ---- tg_rc_ff on rc_ff2_kernel: 16 tokens per wave on 16x16x32 MFMAs (A fragment: lane (r = lane & 15, g = lane >> 4) holds row r, k = 8 g + e) -------
+def _ff2_out_row():
+    """MFMA row r of output tile t = 2 s + u -> offset of its channel inside the 32-channel group s, per u: accumulator register i of lane group g
+    (row 4 g + i) holds channel 32 s + 8 g + 4 u + i — elements 4 u + i of the rows' 16-byte B piece s"""
+    r = torch.arange(16)
+    return torch.stack([8 * (r >> 2) + 4 * u + (r & 3) for u in range(2)])                            # [u, r]
+
+
+def pack_ff2(w1, b1, gamma, beta, w2, b2):
+    """As ``pack_ff`` for ``rc_ff2_kernel`` (same folds, same sizes: 41 KiB + 20 KiB per 32-channel hidden slice j, 3 KiB pad):
+      * w1 stream: 20 VALUE fragments k = 2 s + u, 20 GATE fragments, lane (r, g), element e = W'[32 j + 16 u + r (+ inner), 32 s + 8 g + e]; then the
+        1-KiB page: fp32 bias_a[32], bias_g[32] in hidden-channel order;
+      * w2 stream: 20 fragments, tile t = 2 s + u: lane (r, g), element e = net.2[32 s + 8 (r >> 2) + 4 u + (r & 3), 32 j + 16 (e >> 2) + 4 g + (e & 3)]
+        (the hidden piece a lane group holds after GEGLU: registers i of the two 16-channel value tiles);
+      * b2: fp32 [320]."""
+    inner = w2.shape[1]
+    assert w1.shape == (2 * inner, C) and w2.shape == (C, inner) and inner % 32 == 0
+    dev, dt = w1.device, w1.dtype
+    ar = lambda k: torch.arange(k, device=dev)
+    w1f = w1.detach().float()
+    w1g = (w1f * gamma.detach().float()[None, :]).to(dt)                                 # rounded once, like pack_ln_linear
+    v1 = w1f @ beta.detach().float() + (b1.detach().float() if b1 is not None else 0.0)  # [2 * inner]
+    ns = inner // 32
+    # frag[slice, which, s, u, g, r, e]
+    rows = (inner * ar(2)[None, :, None, None, None, None, None] + 32 * ar(ns)[:, None, None, None, None, None, None]
+            + 16 * ar(2)[None, None, None, :, None, None, None] + ar(16)[None, None, None, None, None, :, None])
+    cols = 32 * ar(10)[None, None, :, None, None, None, None] + 8 * ar(4)[None, None, None, None, :, None, None] + ar(8)
+    fb = w1g[rows, cols].contiguous().reshape(ns, -1).view(torch.uint8)                  # [slice, 40 KiB]
+    page = torch.zeros(ns, 256, dtype=torch.float32, device=dev)
+    page[:, :32] = v1[:inner].reshape(ns, 32)
+    page[:, 32:64] = v1[inner:].reshape(ns, 32)
+    s1 = torch.cat([fb, page.view(torch.uint8)], dim=1).reshape(-1)
+    s1 = torch.cat([s1, torch.zeros(3 * 1024, dtype=torch.uint8, device=dev)])
+    orow = _ff2_out_row().to(dev)                                                        # [u, r]
+    out_rows = (32 * ar(10)[:, None, None] + orow[None]).reshape(20, 16)                 # [t = 2 s + u, r]
+    e = ar(8)
+    kcol = (32 * ar(ns)[:, None, None] + 4 * ar(4)[None, :, None] + (16 * (e >> 2) + (e & 3))[None, None, :])   # [slice, g, e]
+    f2 = w2.detach()[out_rows[None, :, None, :, None], kcol[:, None, :, None, :]].contiguous()                  # [slice, t, g, r, e]
+    s2 = f2.reshape(-1).view(torch.uint8)
+    bb2 = (b2.detach().float() if b2 is not None else torch.zeros(C, device=dev)).contiguous()
+    return s1.contiguous(), s2.contiguous(), bb2
+
+
+def pack_po2(w, b=None):
+    """``proj_out`` [320, 320] (+ bias) -> the tail stream of ``rc_ff2_kernel``: per 32-channel output group st 20 fragments k = 2 s + u (lane (r, g),
+    element e = W[32 st + 8 (r >> 2) + 4 u + (r & 3), 32 s + 8 g + e]) and a 1-KiB page with the fp32 bias in tile order (index 16 u + r); 3 KiB of
+    zero padding behind the last group (every 21-KiB group is fetched as a 24-KiB stage)."""
+    assert w.shape == (C, C)
+    dev = w.device
+    ar = lambda k: torch.arange(k, device=dev)
+    orow = _ff2_out_row().to(dev)                                                        # [u, r]
+    # frag[st, s, u, g, r, e]
+    rows = 32 * ar(10)[:, None, None, None, None, None] + orow[None, None, :, None, :, None]
+    cols = 32 * ar(10)[None, :, None, None, None, None] + 8 * ar(4)[None, None, None, :, None, None] + ar(8)
+    fb = w.detach()[rows, cols].contiguous().reshape(10, -1).view(torch.uint8)           # [st, 20 KiB]
+    page = torch.zeros(10, 256, dtype=torch.float32, device=dev)
+    if b is not None:
+        page[:, :32] = b.detach().float()[(32 * ar(10)[:, None, None] + orow[None]).reshape(10, 32)]
+    out = torch.cat([fb, page.view(torch.uint8)], dim=1).contiguous().reshape(-1)
+    return torch.cat([out, torch.zeros(3 * 1024, dtype=torch.uint8, device=dev)])

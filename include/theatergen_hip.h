@@ -245,6 +245,34 @@ int tg_attention(const tg_attn_desc* d, void* stream);
  *   TG_ERR_LAUNCH       the device refuses the kernel's dynamic LDS (96 KiB per workgroup at head_dim 512) or the launch.
  * Additive to ABI 308: one new symbol, tg_attn_desc unchanged, TG_ABI_VERSION unchanged. */
 int tg_attention_wide(const tg_attn_desc* d, void* stream);
+/* KEY-SPLIT execution of tg_attention_wide for grids under one wave of workgroups.  The unsplit grid is ceil(n_q / 128) x heads x batch x (head_dim / 256)
+ * workgroups on 256 CUs at one workgroup per CU (64 at the VAE's 512 x 512 decode: n_q = len0 = 4096, head_dim 512), each walking all nt = ceil(len0 / 32)
+ * key tiles in turn.  With S splits, S workgroups share one (batch, head, query block, column part); split s runs the same online-softmax loop over the
+ * tiles [s nt / S, (s + 1) nt / S) and stores its UNNORMALISED fp32 accumulators, relative to its own running max m_s (raw score units), and the pair
+ * (m_s, l_s) per query row; a second launch on the same stream combines them:
+ *     M = max_s m_s,   w_s = exp2((m_s - M) scale log2 e),   out = sum_s w_s o_s / sum_s w_s l_s
+ * in fp32, s ascending, rounded once to the storage dtype.  Both launches are plain stores and loads across a kernel boundary (no atomics, no arrival
+ * counters), so the result is deterministic: the same descriptor and S give the same bits, and a batch item's result does not depend on the batch.
+ * It is NOT bit-equal to the unsplit kernel's (another summation order); the error contract is the unsplit kernel's.  `out` is written exactly where
+ * tg_attention_wide writes it.
+ * Workspace: fp32, caller-owned, 16-byte aligned, R = ceil(n_q / 128) * 128 rows per (split, batch, head):
+ *     o  [S][batch][heads][R][head_dim]   then   ml [S][batch][heads][R][2] = (m_s, l_s)
+ *     bytes = S * batch * heads * R * (head_dim + 2) * 4        (33.7 MB for batch 1, n_q 4096, head_dim 512, S = 4)
+ * Rows [n_q, R) are written by the partial launch and never read; nothing past `bytes` is touched.  The contents mean nothing between calls.
+ *
+ * tg_attention_wide_splits: host only, no HIP call.  requested >= 1 -> min(requested, nt) (no split is ever empty; every tile holds >= 8 valid keys).
+ *     requested == 0 -> the planner: with blocks = the unsplit grid, the smallest S in 1 .. 8 that minimises ceil(blocks S / 256) * ceil(nt / S) among those
+ *     with floor(nt / S) >= 8 tiles (256 keys) per split and blocks S <= 512; S = 1 whenever blocks >= 256.  A function of (batch, heads, head_dim, n_q,
+ *     len0) alone — unless the dev knob TG_ATTN_WIDE_SPLIT=n (n >= 1; read at every call) is set, which makes the planner answer min(n, nt).
+ *     Negative: the code tg_attention_wide returns for the same descriptor (every one of its checks runs, pointers included), or TG_ERR_ARG for requested < 0.
+ * tg_attention_wide_workspace_bytes: the byte count above for min(splits, nt) splits; 0 for splits <= 1, an effective split count of 1, or a refused descriptor.
+ * tg_attention_wide_split: every check of tg_attention_wide, then TG_ERR_ARG for splits < 1 and — when min(splits, nt) > 1 — for a NULL or not 16-byte
+ *     aligned workspace or workspace_bytes below the requirement; all before any launch, a refused call writes nothing.  One effective split runs the
+ *     unsplit kernel (bit-equal to tg_attention_wide) and touches no workspace.
+ * Additive to ABI 308: three new symbols, tg_attn_desc unchanged, TG_ABI_VERSION unchanged. */
+int tg_attention_wide_splits(const tg_attn_desc* d, int32_t requested);
+int64_t tg_attention_wide_workspace_bytes(const tg_attn_desc* d, int32_t splits);
+int tg_attention_wide_split(const tg_attn_desc* d, int32_t splits, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Reverse pass of SELF-attention without materialised probabilities (round 5, ABI 306; csrc/tg_attention_bwd.hip), head_dim <= 64, n % 8 == 0:
  *     dQ = dS K,  dK = dS^T Q,  dV = P^T dO   with  P = softmax(scale Q K^T),  dS = scale P o (dO V^T - rowsum(P o dO V^T))

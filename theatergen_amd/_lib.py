@@ -139,6 +139,9 @@ SIGNATURES = {
     "tg_gemm_kernel_name": (C.c_char_p, [C.POINTER(GemmDesc)]),
     "tg_attention": (i32, [C.POINTER(AttnDesc), vp]),
     "tg_attention_wide": (i32, [C.POINTER(AttnDesc), vp]),
+    "tg_attention_wide_splits": (i32, [C.POINTER(AttnDesc), i32]),
+    "tg_attention_wide_workspace_bytes": (i64, [C.POINTER(AttnDesc), i32]),
+    "tg_attention_wide_split": (i32, [C.POINTER(AttnDesc), i32, vp, i64, vp]),
     "tg_attention_bwd": (i32, [C.POINTER(AttnBwdDesc), vp]),
     "tg_attention_bwd_cross": (i32, [C.POINTER(AttnBwdCrossDesc), vp]),
     "tg_attention_bwd_wide": (i32, [C.POINTER(AttnBwdDesc), vp]),

@@ -130,6 +130,10 @@ HOT_GATES = [
     ("attention_kernel<", 0, 256),
     # head dims 256 / 512 (tg_attention_wide.hip, template <T, D, DO>): one wave per SIMD, Q fragment D / 4 registers + O^T accumulator DO / 2.  Scratch 0 is what
     # chose DO = 256 at d = 512 (<T,512,256>: 256 VGPRs + 208 AGPRs; the full-width <T,512,512> instance spilled 996 bytes inside the key loop)
+    # the combine of the key-split partials (<T, D>): a streaming kernel, S loads per thread; scratch would mean its 4-float accumulator left the registers.
+    # Ahead of the kernel gate only in the list: "attention_wide_kernel<" is not a substring of its name.  The SPLIT = true instances of the
+    # main kernel (<T, D, DO, true>: fp32 partial epilogue) fall under the same 0-scratch / 256-VGPR gate as the unsplit ones
+    ("attention_wide_combine_kernel<", 0, 64),
     ("attention_wide_kernel<", 0, 256),
     ("gemm_glds_kernel<", 0, 256),                                 # the LDS-DMA GEMM family: no scratch anywhere
     ("conv_halo_kernel<", 0, 256),

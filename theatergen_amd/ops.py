@@ -57,7 +57,7 @@ class workspace_slot:
 
 
 def workspace(nbytes, device):
-    """Persistent fp32 scratch per (device, slot) (split-K partials, GroupNorm partial sums)."""
+    """Persistent fp32 scratch per (device, slot) (split-K partials, GroupNorm partial sums, the key-split partials of ``attention_wide``)."""
     key = (device.index, "ws", _ws_slot)
     buf = _workspaces.get(key)
     if buf is None or buf.numel() * 4 < nbytes:
@@ -507,9 +507,12 @@ def attention(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch,
     return out
 
 
-def attention_wide(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale, out, out_ld, out_bs):
+def attention_wide(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale, out, out_ld, out_bs, key_splits=None):
     """``tg_attention_wide``: one-segment flash attention for head dims 256 / 512 (the VAE mid block), the argument list of ``attention`` without
-    the second segment, mask, causal flag and device scalar.  Another head dim is an error (``attention`` takes multiples of 8 up to 160)."""
+    the second segment, mask, causal flag and device scalar.  Another head dim is an error (``attention`` takes multiples of 8 up to 160).
+    ``key_splits``: None / 1 = the unsplit launch; 0 = the planner's choice (``tg_attention_wide_splits``), n >= 2 = n splits (clamped to the number of
+    32-key tiles).  More than one effective split runs ``tg_attention_wide_split``: a partial launch and a combine launch, fp32 partials in the
+    persistent ``workspace`` of the current slot (``tg_attention_wide_workspace_bytes``)."""
     _need_cuda(q)
     d = AttnDesc()
     d.dtype = _dt(q)
@@ -520,18 +523,40 @@ def attention_wide(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, b
     d.len0 = int(len0)
     d.scale = float(scale)
     d.out, d.out_ld, d.out_bs = _ptr(out), int(out_ld), int(out_bs)
+    L = _lib.lib()
+    S = 1
+    if key_splits is not None and int(key_splits) != 1:
+        if int(key_splits) < 0:
+            raise RuntimeError(f"attention_wide: key_splits must be None, 0 (planner) or >= 1, got {key_splits}")
+        S = L.tg_attention_wide_splits(C.byref(d), int(key_splits))
+        if S < 0:
+            _lib.check(S)                                                    # a refused descriptor: the code and message of the library
+    if S > 1:
+        nbytes = int(L.tg_attention_wide_workspace_bytes(C.byref(d), S))
+        ws = workspace(nbytes, q.device)
+        launch = lambda: _lib.check(L.tg_attention_wide_split(C.byref(d), S, ws.data_ptr(), ws.numel() * 4, _stream()))   # noqa: E731
+    else:
+        launch = lambda: _lib.check(L.tg_attention_wide(C.byref(d), _stream()))                                            # noqa: E731
     if _gemm_profile is None:
-        _lib.check(_lib.lib().tg_attention_wide(C.byref(d), _stream()))
+        launch()
         return out
     # profiling mode (bench.py roofline leg), as ``attention``: algorithmic flops = QK^T + PV, no recomputed column half counted
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    _lib.check(_lib.lib().tg_attention_wide(C.byref(d), _stream()))
+    launch()
     e1.record()
-    _gemm_profile.append(dict(kernel=f"attention_wide_kernel<d{int(head_dim)}>", splits=1,
-                              M=int(batch) * int(n_q), N=int(heads) * int(head_dim), K=int(len0),
-                              flops=4.0 * batch * heads * n_q * len0 * head_dim, events=(e0, e1), has_res=False,
-                              n_out=int(heads) * int(head_dim), attention=True, batch=int(batch)))
+    rec = dict(splits=S, M=int(batch) * int(n_q), N=int(heads) * int(head_dim), K=int(len0), has_res=False,
+               n_out=int(heads) * int(head_dim), attention=True, batch=int(batch))
+    if S == 1:
+        _gemm_profile.append(dict(rec, kernel=f"attention_wide_kernel<d{int(head_dim)}>", flops=4.0 * batch * heads * n_q * len0 * head_dim, events=(e0, e1)))
+        return out
+    # the C call issues the partial and the combine launch back to back, so the events around it time the PAIR: that time is on the partial's row (with
+    # the algorithmic flops), the combine's row is the launch record with the (empty) interval after it
+    e2 = torch.cuda.Event(enable_timing=True)
+    e2.record()
+    _gemm_profile.append(dict(rec, kernel=f"attention_wide_kernel<d{int(head_dim)},split{S}>", flops=4.0 * batch * heads * n_q * len0 * head_dim,
+                              events=(e0, e1), includes_combine=True))
+    _gemm_profile.append(dict(rec, kernel=f"attention_wide_combine_kernel<d{int(head_dim)}>", flops=0.0, events=(e1, e2), timed_with_partial=True))
     return out
 
 

@@ -15,7 +15,9 @@ folded into the conv gather, 1x1 shortcut GEMMs with the residual in the epilogu
 attention (4096 tokens) is outside the fused flash kernel's register budget and runs once per image: fused Q|K|V^T
 projection GEMM -> scores GEMM -> ``tg_softmax_rows`` -> PV GEMM -> output projection with the residual fused.
 Opt-in (``TG_VAE_FLASH=1`` or ``flash=True``): one Q|K|V^T projection GEMM and ONE flash launch for the whole batch
-(``tg_attention_wide`` at C = 256 / 512, ``tg_attention`` at C <= 160), no [N, N] scores tensor.
+(``tg_attention_wide`` at C = 256 / 512, ``tg_attention`` at C <= 160), no [N, N] scores tensor.  On top of it, opt-in
+(``TG_VAE_FLASH_SPLIT=1`` or ``flash_split=True`` / an int >= 2): the wide launch splits its key range over several workgroups where
+its grid is under one wave of them (``tg_attention_wide_split``: fp32 partials in the persistent workspace, a combine launch).
 """
 import os
 from types import SimpleNamespace
@@ -51,10 +53,13 @@ def tiny_vae_config():
 class VAEAttention(nn.Module):
     """diffusers ``Attention(C, heads=1, dim_head=C, bias=True, norm_num_groups=32, residual_connection=True)``"""
 
-    def __init__(self, channels, groups=32, eps=1e-6, flash=None):
+    def __init__(self, channels, groups=32, eps=1e-6, flash=None, flash_split=None):
         super().__init__()
         self.channels, self.groups, self.eps = channels, groups, eps
         self.flash = flash                      # True / False, or None: the environment's TG_VAE_FLASH=1 decides (default off)
+        # key split of the flash route's ``attention_wide`` launch (C = 256 / 512 only; the C <= 160 and the materialised routes ignore it):
+        # True = the planner decides per shape, an int >= 2 = that many splits, False = off, None: TG_VAE_FLASH_SPLIT=1 means True (default off)
+        self.flash_split = flash_split
         self.group_norm = nn.GroupNorm(groups, channels, eps=eps)
         self.to_q = nn.Linear(channels, channels)
         self.to_k = nn.Linear(channels, channels)
@@ -67,6 +72,15 @@ class VAEAttention(nn.Module):
         on = self.flash if self.flash is not None else os.environ.get("TG_VAE_FLASH") == "1"
         C = self.channels
         return bool(on) and ((C <= 160 and C % 8 == 0) or C in (256, 512))
+
+    def key_splits(self):
+        """``ops.attention_wide``'s ``key_splits`` for this module: None (unsplit), 0 (planner) or n >= 2"""
+        fs = self.flash_split if self.flash_split is not None else os.environ.get("TG_VAE_FLASH_SPLIT") == "1"
+        if fs is True:
+            return 0
+        if fs is False or fs is None or int(fs) < 2:
+            return None
+        return int(fs)
 
     def _run_flash(self, x: _Act):
         """GroupNorm -> one GEMM (Q | K rows + V^T, as ``attention_processor.qkv_weight`` / ``self_attention_from_qkv``) -> one flash launch for
@@ -81,8 +95,11 @@ class VAEAttention(nn.Module):
         vt = torch.empty((B, C, N), dtype=y.dtype, device=y.device)
         ops.gemm(y, wqkv, B * N, 3 * C, C, bias=bqkv, rows_per_batch=N, out=qk, n_split=2 * C, out_t=vt, ldt=N)
         o = torch.empty((B * N, C), dtype=y.dtype, device=y.device)
-        attn = ops.attention if C <= 160 else ops.attention_wide
-        attn(qk, 2 * C, N * 2 * C, qk[:, C:], 2 * C, N * 2 * C, vt, N, C * N, N, B, 1, C, N, float(C) ** -0.5, o, C, N * C)
+        if C <= 160:
+            ops.attention(qk, 2 * C, N * 2 * C, qk[:, C:], 2 * C, N * 2 * C, vt, N, C * N, N, B, 1, C, N, float(C) ** -0.5, o, C, N * C)
+        else:
+            ops.attention_wide(qk, 2 * C, N * 2 * C, qk[:, C:], 2 * C, N * 2 * C, vt, N, C * N, N, B, 1, C, N, float(C) ** -0.5, o, C, N * C,
+                               key_splits=self.key_splits())
         out = ops.linear(o, self.to_out[0].weight, self.to_out[0].bias, res=x.t)
         return _Act(out, x.b, x.h, x.w, C)
 
@@ -118,14 +135,14 @@ class _UpBlock(nn.Module):
 
 
 class Decoder(nn.Module):
-    def __init__(self, cfg, flash=None):
+    def __init__(self, cfg, flash=None, flash_split=None):
         super().__init__()
         boc = tuple(cfg.block_out_channels)
         g = cfg.norm_num_groups
         self.conv_in = nn.Conv2d(cfg.latent_channels, boc[-1], 3, padding=1)
         mid = nn.Module()
         mid.resnets = nn.ModuleList([ResnetBlock2D(boc[-1], boc[-1], None, g, 1e-6), ResnetBlock2D(boc[-1], boc[-1], None, g, 1e-6)])
-        mid.attentions = nn.ModuleList([VAEAttention(boc[-1], g, 1e-6, flash)])
+        mid.attentions = nn.ModuleList([VAEAttention(boc[-1], g, 1e-6, flash, flash_split)])
         self.mid_block = mid
         self.up_blocks = nn.ModuleList()
         rboc = tuple(reversed(boc))
@@ -168,7 +185,7 @@ class Encoder(nn.Module):
     ResnetBlock2D(temb=None, eps 1e-6) + a padding-0 downsample on all but the last), UNetMidBlock2D (1 head), GroupNorm ->
     SiLU -> conv_out to 2 * latent_channels."""
 
-    def __init__(self, cfg, flash=None):
+    def __init__(self, cfg, flash=None, flash_split=None):
         super().__init__()
         boc = tuple(cfg.block_out_channels)
         g = cfg.norm_num_groups
@@ -185,7 +202,7 @@ class Encoder(nn.Module):
             prev = c
         mid = nn.Module()
         mid.resnets = nn.ModuleList([ResnetBlock2D(boc[-1], boc[-1], None, g, 1e-6), ResnetBlock2D(boc[-1], boc[-1], None, g, 1e-6)])
-        mid.attentions = nn.ModuleList([VAEAttention(boc[-1], g, 1e-6, flash)])
+        mid.attentions = nn.ModuleList([VAEAttention(boc[-1], g, 1e-6, flash, flash_split)])
         self.mid_block = mid
         self.conv_norm_out = nn.GroupNorm(g, boc[-1], eps=1e-6)
         self.conv_out = nn.Conv2d(boc[-1], 2 * cfg.latent_channels, 3, padding=1)
@@ -232,15 +249,17 @@ class DecoderOutput(SimpleNamespace):
 
 
 class AutoencoderKL(nn.Module):
-    def __init__(self, config=None, flash=None, **kw):
-        """``flash``: the mid blocks' attention route (``VAEAttention.flash``): True / False, or None = ``TG_VAE_FLASH=1`` decides (default off)"""
+    def __init__(self, config=None, flash=None, flash_split=None, **kw):
+        """``flash``: the mid blocks' attention route (``VAEAttention.flash``): True / False, or None = ``TG_VAE_FLASH=1`` decides (default off).
+        ``flash_split``: the key split of that route's wide launch (``VAEAttention.flash_split``): True = planner, int >= 2 = forced, None =
+        ``TG_VAE_FLASH_SPLIT=1`` decides (default off)"""
         super().__init__()
         self.config = config if config is not None else sd_vae_config(**kw)
         lc = self.config.latent_channels
-        self.encoder = Encoder(self.config, flash)
+        self.encoder = Encoder(self.config, flash, flash_split)
         self.quant_conv = nn.Conv2d(2 * lc, 2 * lc, 1)
         self.post_quant_conv = nn.Conv2d(lc, lc, 1)
-        self.decoder = Decoder(self.config, flash)
+        self.decoder = Decoder(self.config, flash, flash_split)
         self._p = _Packed()
         for p_ in self.parameters():
             p_.requires_grad_(False)
@@ -324,9 +343,9 @@ class AutoencoderKL(nn.Module):
         return DecoderOutput(sample=img)
 
     @classmethod
-    def from_state_dict(cls, config, state_dict, device="cuda", dtype=torch.bfloat16, flash=None):
+    def from_state_dict(cls, config, state_dict, device="cuda", dtype=torch.bfloat16, flash=None, flash_split=None):
         """a decoder-only state dict (no ``encoder.*`` keys) builds a decode-only module"""
-        m = cls(config, flash=flash)
+        m = cls(config, flash=flash, flash_split=flash_split)
         if not any(k.startswith("encoder.") for k in state_dict):
             del m.encoder, m.quant_conv
             m.encoder = m.quant_conv = None

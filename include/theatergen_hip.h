@@ -593,7 +593,7 @@ int tg_guidance_plan_run(const tg_guidance_pitem* items_device, int32_t n_items,
  * (ip_adapter/attention_processor.py:113-128) and `Transformer2DModel.proj_in / proj_out` (models/transformer_2d.py:150-163) at the
  * first UNet level.  `wpk`: N / 64 chunks of (128 K + 1024) bytes: the chunk's weight fragments, then one vector page (fp32 v[64]:
  * bias, or W beta + bias with the fold; fp32 u[64]: row sums of the rounded W gamma, fold only).  `ln` != 0: x is the UN-normalised
- * stream, statistics per row in fp32 (two-pass, as tg_layernorm).  `variant`: dev switch between workgroup shapes / schedules. */
+ * stream, statistics per row in fp32 (two-pass, as tg_layernorm).  `variant`: reserved, must be 0. */
 typedef struct {
   int32_t dtype;
   const void* x; int64_t ldx;
@@ -642,7 +642,7 @@ int tg_rc_kv_pack(int32_t dtype, int32_t batch, const void* k, const void* vt, i
  * `wpo` != NULL also Transformer2DModel.proj_out + its residual (models/transformer_2d.py:316-327), in one launch:
  *     h3 = net2(a * gelu(g)) + b2 + h,  [a | g] = proj(LayerNorm(h)) + b1;      out = wpo ? proj_out(h3) + b + res0 : h3
  * `w1` / `w2` / `b2`: theatergen_amd/rowchain.py::pack_ff (LayerNorm gamma / beta folded into proj; the kernel normalises the rows);
- * `wpo`: rc_pack_tiles stream of proj_out (+ bias).  `inner` = the hidden width (1280).  `dbg`: dev timing switches in the low 16 bits, 0;
+ * `wpo`: rc_pack_tiles stream of proj_out (+ bias).  `inner` = the hidden width (1280).  `dbg`: reserved, must be 0, but for one bit:
  * TG_RC_FF_TWO_WAVE selects the kernel that runs two waves per SIMD (one 8-wave workgroup per 128 tokens, 16 tokens per wave on 16x16x32 MFMAs):
  * `w1` / `w2` are then rowchain.py::pack_ff2 streams and `wpo` a pack_po2 stream (other fragment order, same sizes). */
 #define TG_RC_FF_TWO_WAVE 0x10000
@@ -679,7 +679,7 @@ typedef struct {
   int64_t M;
   int32_t rows_per_batch;
   float ln_eps;
-  int32_t dbg;     /* dev timing switches, 0 */
+  int32_t dbg;     /* reserved, must be 0 */
 } tg_rc_front_desc;
 int tg_rc_front(const tg_rc_front_desc* d, void* stream);
 

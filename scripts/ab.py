@@ -2,7 +2,7 @@
 """Same-box A/B of LIBRARY BUILDS (old .so vs new .so) and / or environment switches, interleaved, graph-replayed bench.
 
     python scripts/ab.py --rounds 3 --out gpurun_out/ab_attn.json \
-        --variant r3:lib=theatergen_amd/lib/libtheatergen_hip_r3.so --variant new --variant pipe:TG_ATTN_PIPE=1
+        --variant r3:lib=theatergen_amd/lib/libtheatergen_hip_r3.so --variant new --variant rc_off:TG_RC=0
 
 A variant is  name[:key=value[,key=value...]]  where key `lib` selects the shared library (THEATERGEN_HIP_LIB) and every other
 key is an environment variable.  Box-to-box spread of the pool is +-4 %, so only interleaved runs on ONE box decide anything
@@ -48,7 +48,8 @@ def main():
                 res[name].append(d["ms_per_step"])
                 print(f"round {r} {name}: {d['value']} {d['unit']}  {d['ms_per_step']} ms/step", flush=True)
             except (IndexError, ValueError, KeyError):
-                print(f"round {r} {name}: FAILED\n{p.stderr[-800:]}", flush=True)
+                print(f"round {r} {name}: FAILED (exit status {p.returncode})\n{p.stderr[-800:]}", flush=True)
+                raise SystemExit(1)                  # nothing more is started on a GPU that a run may have faulted
     summary = {n: {"ms_per_step": v, "median": statistics.median(v) if v else None} for n, v in res.items()}
     base = summary[variants[0][0]]["median"]
     for n, s in summary.items():

@@ -33,8 +33,6 @@ def run(M, dtype, proj, time_it=True, inner=1280):
     if time_it:
         out = torch.empty_like(got)
         row["rc_ff_us"] = round(timeit(lambda i: ops.rc_ff(h, s1, s2, bb2, inner, 1e-5, wpo=wpo, res0=x0 if proj else None, out=out), n=10), 1)
-        for dbg in (1, 2, 4, 3, 6, 7, 7 | 8, 7 | 8 | 16):
-            row[f"dbg{dbg}_us"] = round(timeit(lambda i: ops.rc_ff(h, s1, s2, bb2, inner, 1e-5, wpo=wpo, res0=x0 if proj else None, out=out, dbg=dbg), n=5), 1)
         # current path: layernorm + GEGLU GEMM + net.2 GEMM (+ proj_out GEMM)
         w1p, b1p = pack_geglu(w1, b1)
         hb = torch.empty(M, inner, device=dev, dtype=dtype); h3b = torch.empty(M, C, device=dev, dtype=dtype); ob = torch.empty(M, C, device=dev, dtype=dtype)

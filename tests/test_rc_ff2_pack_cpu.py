@@ -107,3 +107,18 @@ def test_two_wave_kernel_is_the_default_and_switchable():
         assert rowchain.MODE & 32 and rowchain.MODE & 15 == 15
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "theatergen_hip.h")).read()
     assert f"#define TG_RC_FF_TWO_WAVE 0x{rowchain.FF_TWO_WAVE:x}" in header
+
+
+def test_retired_switch_names_are_gone():
+    """the A/B arms that lost were deleted with their switches (profiles/retired_arms_findings.md): no source of the package names one any more"""
+    import glob
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    retired = ["TG_NO_GN_FUSE", "TG_NO_LN_FUSE", "TG_LN_MODE", "TG_LN_FF_MAX_ROWS", "TG_CONV_OUT_GN", "TG_FF_PAD", "TG_RESAMPLER_SIDE", "TG_CONV_IN_MFMA",
+               "TG_CONV_OUT_MFMA", "TG_ATTN_NOFOLD", "TG_ATTN_PIPE", "TG_RC_DEV", "TG_RC_DEV_BUILD"]
+    files = (glob.glob(os.path.join(root, "theatergen_amd", "**", "*.py"), recursive=True) + glob.glob(os.path.join(root, "theatergen_amd", "csrc", "*"))
+             + glob.glob(os.path.join(root, "include", "*")))
+    files = [f for f in files if os.path.isfile(f)]
+    assert len(files) > 40
+    hits = [(os.path.relpath(f, root), name) for f in files for text in [open(f, errors="replace").read()] for name in retired if name in text]
+    assert not hits, hits

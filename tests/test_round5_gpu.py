@@ -219,18 +219,37 @@ def test_ip_scale_assignment_is_fenced_against_engine_streams():
 
 
 def test_row_chain_dev_switches_are_rejected_in_release_calls():
-    """the timing switches of the row-chain kernels (skip stores / barriers / MFMAs) ride in descriptor bits; without TG_RC_DEV=1 in the
-    environment a descriptor that carries them is an argument error, not a silently wrong result"""
+    """the timing switches of the row-chain kernels (skip stores / barriers / MFMAs) rode in descriptor bits.  The switches are gone and the
+    words they rode in are reserved: a descriptor that sets one is an argument error raised before any launch (the sentinel outputs stay untouched),
+    not a silently wrong result"""
     from theatergen_amd import ops
     from theatergen_amd.weights_pack import rc_pack
-    if os.environ.get("TG_RC_DEV") == "1":
-        pytest.skip("dev switches enabled in this environment")
-    x = torch.randn(256, 320, device=DEV).to(torch.bfloat16)
-    w = (torch.randn(320, 320, device=DEV) / 18).to(torch.bfloat16)
+    bf = torch.bfloat16
+    x = torch.randn(256, 320, device=DEV).to(bf)
+    w = (torch.randn(320, 320, device=DEV) / 18).to(bf)
     wpk = rc_pack(w, None)
     ops.rc_linear(x, wpk, 320)
+    # the smallest operands the wrappers accept: 128 rows x 320 channels, inner = 64, 77 text keys (nothing is launched: zeros of the stream sizes do)
+    h = x[:128]
+    u8 = lambda n: torch.zeros(n, dtype=torch.uint8, device=DEV)
+    sentinel = lambda *shape: torch.full(shape, 7.0, dtype=bf, device=DEV)
+    tiles = lambda n: u8(n * 21 * 1024 + 3072)
+    out, y, qk, vt = sentinel(128, 320), sentinel(128, 320), sentinel(128, 640), sentinel(1, 320, 128)
+    coef = torch.zeros(1, 2, 320, device=DEV)
+    kv = torch.zeros(1, 8, 24 * 512, dtype=bf, device=DEV)
     with pytest.raises(RuntimeError):
-        ops.rc_linear(x, wpk, 320, variant=256)
+        ops.rc_linear(h, wpk, 320, out=out, _reserved=256)
+    with pytest.raises(RuntimeError):
+        ops.rc_linear(h, wpk, 320, out=out, _reserved=1)
+    with pytest.raises(RuntimeError):
+        ops.rc_front(h, coef, tiles(10), tiles(30), 128, 1e-5, y=y, qk=qk, vt=vt, _reserved=256)
+    with pytest.raises(RuntimeError):
+        ops.rc_ff(h, u8(2 * 41 * 1024 + 3072), u8(2 * 20 * 1024), torch.zeros(320, device=DEV), 64, 1e-5, out=out, _reserved=1)
+    with pytest.raises(RuntimeError):
+        ops.rc_xattn(h, tiles(10), kv, tiles(10), 128, 1e-5, 4, out=out, text_len=77 + 256)
+    torch.cuda.synchronize()
+    for t in (out, y, qk, vt):
+        assert bool((t == 7.0).all()), "a refused call wrote its output"
 
 
 def test_skinny_gemm_large_k_instances_after_the_register_fix():

@@ -123,10 +123,10 @@ def build(force=False, verbose=True, check_gate=False):
 RESOURCES_JSON = os.path.join(os.path.dirname(HERE), "profiles", "r6_kernel_resources.json")
 # (substring of the DEMANGLED name, max scratch bytes / lane, max VGPRs)
 HOT_GATES = [
-    # SD-1.5 level 0 (d = 40): four waves per SIMD, nothing spilled.  Template arguments: <T, DPAD, DV, ONES, FOLD, PIPE, MASK> (round 4 added the last
-    # two; the round-4 strings matched no kernel — ADVICE r4 — and check_resources now fails on a gate that matches nothing)
-    ("attention_kernel<bf16,48,64,true,true,false,false>", 0, 128),
-    ("attention_kernel<f16,48,64,true,true,false,false>", 0, 128),
+    # SD-1.5 level 0 (d = 40): four waves per SIMD, nothing spilled.  Template arguments: <T, DPAD, DV, ONES, FOLD, MASK> (check_resources fails on a
+    # gate that matches nothing, so a changed parameter list cannot switch these two off silently)
+    ("attention_kernel<bf16,48,64,true,true,false>", 0, 128),
+    ("attention_kernel<f16,48,64,true,true,false>", 0, 128),
     ("attention_kernel<", 0, 256),
     # head dims 256 / 512 (tg_attention_wide.hip, template <T, D, DO>): one wave per SIMD, Q fragment D / 4 registers + O^T accumulator DO / 2.  Scratch 0 is what
     # chose DO = 256 at d = 512 (<T,512,256>: 256 VGPRs + 208 AGPRs; the full-width <T,512,512> instance spilled 996 bytes inside the key loop)
@@ -146,7 +146,7 @@ HOT_GATES = [
     ("rc_ff_kernel<", 0, 256),
     ("rc_ff2_kernel<", 0, 256),                                    # two waves per SIMD: a 257th register would halve the occupancy the kernel exists for
     ("rc_front_kernel<", 0, 216),                                  # round 4's first version spilled 108 registers (30 % of its launch)
-    ("rc_linear_kernel<", 0, 256),                                 # every instance (the UNet launches <T,20,8,2,false,0>, plain / + residual)
+    ("rc_linear_kernel<", 0, 256),                                 # template arguments <T, KS, NW, LN>: plain / + residual and the LayerNorm fold
     ("skinny_gemm_kernel<", 0, 256),                               # round 5: the CK = 16 / 20 instances spilled 44 .. 164 bytes
     # reverse pass of attention, one kernel template <NKS, OT, T, MODE> (tg_attention_bwd.hip).  <4,2,..> is d <= 64 at two waves per SIMD
     # (round 5; statistics / dQ / dK + dV instances: 156 / 198 / 216 VGPRs).  The rest is 64 < d <= 160 at one wave per SIMD (unified 512-register

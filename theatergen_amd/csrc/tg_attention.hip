@@ -72,7 +72,7 @@ struct AttnParams {
 // MASK (own instantiations, never the hot path): `attention_mask` of the diffusers processors — an additive bias on segment 0's scores
 // (`baddbmm(mask, q, k^T, beta=1, alpha=scale)`, ip_adapter/attention_processor.py:193-206), broadcast over heads and / or queries by
 // zero strides.  It is added in raw-score units (mask / scale) right after the QK^T tile, so the online softmax is unchanged.
-template <typename T, int DPAD, int DV, bool ONES, bool FOLD, bool PIPE, bool MASK>
+template <typename T, int DPAD, int DV, bool ONES, bool FOLD, bool MASK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 3 : (DV <= 96 ? 2 : 1)))) void attention_kernel(AttnParams p) {
   typedef typename Vec<T>::v8 V8;
   typedef typename Vec<T>::v4 V4;
@@ -265,63 +265,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
     else if (p.len1 > 0) issue(kb1, p.k1_ld, vb1, p.vt1_ld, p.len1, 0, st ^ 1);
     const T* sK = sbase + st * STAGE;
     f32x16 s[2];
-    // PIPE (DV = 64 variants: head dims 40 and 64), full tiles only: MFMA and VALU work of ONE wave interleaved in program order.  The
-    // chain QK^T -> max -> exp2 -> convert -> PV is dependent end to end inside a wave, and the rocprofv3 trace of the SD-1.5 step
-    // (5 level-0 self-attention launches of 499 us = 1096 cycles per wave-tile and SIMD against ~450 of VALU + ~450 of matrix pipe)
-    // says the three waves of a SIMD do not hide each other's phases.  So: the second 32-key half's QK^T MFMAs run with the max over
-    // the first half in their shadow, and the PV MFMAs of the first half run with the exp2s of the second half between them (an MFMA
-    // executes asynchronously; the wave keeps issuing independent VALU instructions behind it).  Same arithmetic, same order of
-    // every accumulation: bit-identical to the straight-line path (which ragged / causal tiles keep).  Measured (MI355X, same box,
-    // TG_ATTN_FLAGS 1 / 0): level-0 self-attention in isolation 660 -> 634 us and 719 -> 698 us on two boxes (-3 .. -4 %), the SD-1.5
-    // bench +0.2 .. +0.6 % — at 152 instead of 125 VGPRs (three resident waves per SIMD instead of four).  What it says about the
-    // hardware: a wave-tile costs about the SUM of its VALU and matrix-pipe time whatever the issue order, so the remaining levers
-    // are fewer instructions, not more overlap.
-    // PIPE is a TEMPLATE parameter (its own instantiation, dev switch TG_ATTN_PIPE=1): compiled into the default kernel behind a
-    // run-time flag (round 3) it took the d = 40 kernel from 125 VGPRs / 0 scratch to 168 VGPRs / 6 spills with scratch reloads
-    // inside the tile loop (+30 % per launch) — the default instantiation carries none of it.
-    static_assert(!PIPE || (DV == 64 && NKS <= 3), "PIPE: head dim 40 only");
-    const bool piped = PIPE && !(kv0 + KV > p.len0 || p.causal != 0);
-    float tm;
-    if (piped) {
-      V8 kf0[NKS], kf1[NKS];
+    scores(s, sK, p.len0, kv0, p.causal != 0);
+    if constexpr (MASK) {
+      const float* mp = p.mask + (long)b * p.mask_bs + (long)h * p.mask_hs + (q_ok ? qrow : 0) * p.mask_qs;
 #pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) {
-        kf0[ks] = *reinterpret_cast<const V8*>(sK + kofs[ks & 3] + (ks >> 2) * 4096);
-        kf1[ks] = *reinterpret_cast<const V8*>(sK + kofs[ks & 3] + ((ks >> 2) * 4096 + 32 * 64));
-      }
+      for (int kvt = 0; kvt < 2; ++kvt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) { s[0][r] = 0.f; s[1][r] = 0.f; }
-      float mx = -INFINITY;
-      // S0 chain first, the S1 chain with the max over S0 in its shadow
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) s[0] = mfma32(kf0[ks], qf[ks], s[0]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) {
-        s[1] = mfma32(kf1[ks], qf[ks], s[1]);
-#pragma unroll
-        for (int r = ks * 16 / NKS; r < (ks + 1) * 16 / NKS; ++r) mx = fmaxf(mx, s[0][r]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[1][r]);
-      float a = mx, b2 = mx;
-      asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b2));
-      tm = fmaxf(a, b2);
-    } else {
-      scores(s, sK, p.len0, kv0, p.causal != 0);
-      if constexpr (MASK) {
-        const float* mp = p.mask + (long)b * p.mask_bs + (long)h * p.mask_hs + (q_ok ? qrow : 0) * p.mask_qs;
-#pragma unroll
-        for (int kvt = 0; kvt < 2; ++kvt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int kv = kv0 + kvt * 32 + 16 * (r >> 3) + 8 * hi + (r & 7);
-            if (kv < p.len0) s[kvt][r] += mp[kv] * p.inv_scale;
-          }
-      }
-      tm = tile_max(s);
+        for (int r = 0; r < 16; ++r) {
+          const int kv = kv0 + kvt * 32 + 16 * (r >> 3) + 8 * hi + (r & 7);
+          if (kv < p.len0) s[kvt][r] += mp[kv] * p.inv_scale;
+        }
     }
+    const float tm = tile_max(s);
     // m_run is kept in RAW score units; exp2 arguments are formed as fma(s, c, -m*c) with c = scale * log2(e) > 0.
     // v_exp_f32 directly (__builtin_amdgcn_exp2f): results stay far inside the fp32 range, exp2(-inf) = 0 — none of
     // exp2f()'s denormal-range rescaling (v_ldexp + compares + selects per element) is needed.
@@ -368,61 +323,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
     // exp2 of one score register: FOLD scores are exp2's argument already
     auto ex = [&](float x) { return FOLD ? __builtin_amdgcn_exp2f(x) : __builtin_amdgcn_exp2f(__builtin_fmaf(x, p.scale_log2, -mc)); };
     const T* sV = sK + K_ELEMS;
-    if (piped) {
-      V8 vf[2][DT];                                  // V^T fragments of the first half's two chunks: requested before its exp2s
 #pragma unroll
-      for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int t2 = 0; t2 < DT; ++t2) vf[c][t2] = *reinterpret_cast<const V8*>(sV + vofs[c] + t2 * 32 * 64);
+    for (int kvt = 0; kvt < 2; ++kvt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float e = ex(s[0][r]);
-        s[0][r] = e;
+        const float e = ex(s[kvt][r]);
+        s[kvt][r] = e;
         if (!ONES) ps += e;
       }
-      __builtin_amdgcn_sched_barrier(0);
-      constexpr int EPM = 16 / (2 * DT);             // exp2s of the second half behind every PV MFMA of the first
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        V8 pf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pf[j] = from_f32<T>(s[0][8 * c + j]);
-#pragma unroll
-        for (int t2 = 0; t2 < DT; ++t2) {
-          o[t2] = mfma32(vf[c][t2], pf, o[t2]);
-#pragma unroll
-          for (int r = (c * DT + t2) * EPM; r < (c * DT + t2 + 1) * EPM; ++r) {
-            const float e = ex(s[1][r]);
-            s[1][r] = e;
-            if (!ONES) ps += e;
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-#pragma unroll
-      for (int c = 2; c < 4; ++c) {
-        V8 pf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pf[j] = from_f32<T>(s[1][8 * (c & 1) + j]);
-#pragma unroll
-        for (int t2 = 0; t2 < DT; ++t2) {
-          const V8 vf2 = *reinterpret_cast<const V8*>(sV + vofs[c] + t2 * 32 * 64);
-          o[t2] = mfma32(vf2, pf, o[t2]);
-        }
-      }
-      if (!ONES) l_run += ps;
-    } else {
-#pragma unroll
-      for (int kvt = 0; kvt < 2; ++kvt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float e = ex(s[kvt][r]);
-          s[kvt][r] = e;
-          if (!ONES) ps += e;
-        }
-      if (!ONES) l_run += ps;
-      pv(s, sV);
-    }
+    if (!ONES) l_run += ps;
+    pv(s, sV);
   }
   {
     float l_tot;
@@ -493,14 +403,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
   }
 }
 
-template <typename T, int DPAD, int DV, bool ONES, bool FOLD = false, bool PIPE = false, bool MASK = false>
+template <typename T, int DPAD, int DV, bool ONES, bool FOLD = false, bool MASK = false>
 int launch_attn(const tg_attn_desc* d, const AttnParams& p, hipStream_t st) {
   constexpr int NP = (DPAD + 63) / 64;
   const size_t lds = (size_t)2 * (NP * 64 * 64 + DV * 64) * sizeof(T);
   AttnParams pp = p;
   pp.n_qblk = (d->n_q + 127) / 128;
   dim3 grid((unsigned)(pp.n_qblk * d->heads * d->batch));
-  auto k = attention_kernel<T, DPAD, DV, ONES, FOLD, PIPE, MASK>;
+  auto k = attention_kernel<T, DPAD, DV, ONES, FOLD, MASK>;
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   (void)attr;
   hipLaunchKernelGGL(k, grid, dim3(256), lds, st, pp);
@@ -513,21 +423,18 @@ int dispatch_attn(const tg_attn_desc* d, const AttnParams& p, hipStream_t st) {
   // ONES variants need a spare V^T row (DV > head dim): 40 -> (48, 64), 80 -> (80, 96), <= 16 -> (16, 32)
   const int hd = d->head_dim;
   if (p.mask != nullptr) {
-    if (hd <= 16) return launch_attn<T, 16, 32, true, false, false, true>(d, p, st);
-    if (hd <= 32) return launch_attn<T, 32, 32, false, false, false, true>(d, p, st);
-    if (hd <= 48) return launch_attn<T, 48, 64, true, false, false, true>(d, p, st);
-    if (hd <= 64) return launch_attn<T, 64, 64, false, false, false, true>(d, p, st);
-    if (hd <= 80) return launch_attn<T, 80, 96, true, false, false, true>(d, p, st);
-    if (hd <= 96) return launch_attn<T, 96, 96, false, false, false, true>(d, p, st);
-    if (hd <= 128) return launch_attn<T, 128, 128, false, false, false, true>(d, p, st);
-    return launch_attn<T, 160, 160, false, false, false, true>(d, p, st);
+    if (hd <= 16) return launch_attn<T, 16, 32, true, false, true>(d, p, st);
+    if (hd <= 32) return launch_attn<T, 32, 32, false, false, true>(d, p, st);
+    if (hd <= 48) return launch_attn<T, 48, 64, true, false, true>(d, p, st);
+    if (hd <= 64) return launch_attn<T, 64, 64, false, false, true>(d, p, st);
+    if (hd <= 80) return launch_attn<T, 80, 96, true, false, true>(d, p, st);
+    if (hd <= 96) return launch_attn<T, 96, 96, false, false, true>(d, p, st);
+    if (hd <= 128) return launch_attn<T, 128, 128, false, false, true>(d, p, st);
+    return launch_attn<T, 160, 160, false, false, true>(d, p, st);
   }
   if (hd <= 16) return launch_attn<T, 16, 32, true>(d, p, st);
   if (hd <= 32) return launch_attn<T, 32, 32, false>(d, p, st);
-  if (hd == 40 && !getenv("TG_ATTN_NOFOLD")) {                                                       // bias folded into QK^T (dev switch for A/B)
-    static const bool pipe = getenv("TG_ATTN_PIPE") != nullptr;                                       // dev A/B: the intra-wave interleave instantiation
-    return pipe ? launch_attn<T, 48, 64, true, true, true>(d, p, st) : launch_attn<T, 48, 64, true, true>(d, p, st);
-  }
+  if (hd == 40) return launch_attn<T, 48, 64, true, true>(d, p, st);      // bias folded into QK^T
   if (hd <= 48) return launch_attn<T, 48, 64, true>(d, p, st);
   if (hd <= 64) return launch_attn<T, 64, 64, false>(d, p, st);
   if (hd <= 80) return launch_attn<T, 80, 96, true>(d, p, st);

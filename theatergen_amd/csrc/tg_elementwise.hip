@@ -707,11 +707,8 @@ extern "C" int tg_add(int32_t dtype, const void* a, const void* b, int64_t n, vo
 }
 
 namespace {
-// the matrix-core conv_in kernel takes the channel counts (dev A/B knob TG_CONV_IN_MFMA=0: the fp32-FMA kernels)
-bool conv_in_mfma_ok(int cin, int cout) {
-  static const bool mfma_on = [] { const char* e = getenv("TG_CONV_IN_MFMA"); return !(e && e[0] == '0'); }();
-  return mfma_on && cin == 4 && cout > 0 && cout % 160 == 0 && cout <= 640;
-}
+// the matrix-core conv_in kernel takes the channel counts (the fp32-FMA kernels serve the rest)
+bool conv_in_mfma_ok(int cin, int cout) { return cin == 4 && cout > 0 && cout % 160 == 0 && cout <= 640; }
 
 template <typename T>
 __global__ __launch_bounds__(256) void dup_rows_kernel(const T* src, T* dst, long rows, int cols8, long ld) {
@@ -758,7 +755,7 @@ extern "C" int tg_conv_in_dup(int32_t dtype, const void* sample, int32_t src_dty
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const long npix = (long)batch * h * w;
   {
-    // matrix-core path (round 5): cin = 4, cout a multiple of 160 (dev A/B knob TG_CONV_IN_MFMA=0: the fp32-FMA kernels below)
+    // matrix-core path (round 5): cin = 4, cout a multiple of 160 (other shapes: the fp32-FMA kernels below)
     const bool mfma = conv_in_mfma_ok(cin, cout) && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(weight) & 7) == 0;
     // the second store exists in the matrix-core kernel only: never ignored elsewhere
     TG_CHECK(dup_offset == 0 || (mfma && dup_offset % 8 == 0 && dup_offset >= npix * cout), TG_ERR_ARG,
@@ -813,11 +810,8 @@ extern "C" int tg_conv_in_dup(int32_t dtype, const void* sample, int32_t src_dty
 }
 
 namespace {
-// the matrix-core kernel takes the problem (dev A/B knob TG_CONV_OUT_MFMA=0: the dot-product kernels)
-bool conv_out_mfma_ok(int cin, int h, int w, int cout) {
-  static const bool on = [] { const char* e = getenv("TG_CONV_OUT_MFMA"); return !(e && e[0] == '0'); }();
-  return on && cin % 64 == 0 && cin <= 320 && cout > 0 && cout <= 8 && h % 8 == 0 && w % 16 == 0;
-}
+// the matrix-core kernel takes the problem (the dot-product kernels serve the rest)
+bool conv_out_mfma_ok(int cin, int h, int w, int cout) { return cin % 64 == 0 && cin <= 320 && cout > 0 && cout <= 8 && h % 8 == 0 && w % 16 == 0; }
 }  // namespace
 
 extern "C" int tg_conv_out_takes_coef(int32_t cin, int32_t h, int32_t w, int32_t cout) { return conv_out_mfma_ok(cin, h, w, cout) ? 1 : 0; }

@@ -26,16 +26,7 @@
 #include <type_traits>
 #include <utility>
 
-// Dev timing switches (skip stores / barriers / MFMAs: WRONG results by design) exist only in a build with -DTG_RC_DEV_BUILD; the library's own build
-// (theatergen_amd/build.py) compiles them OUT of the stage loops: RC_DBG(bit) is the constant 0 there and the C entries refuse every dev bit.
-#ifdef TG_RC_DEV_BUILD
-#define RC_DBG(bit) ((p.dbg & (bit)) != 0)
-#define RC_DBG_ARG() (p.dbg >> 8)
-#else
-#define RC_DBG(bit) (false)
-#define RC_DBG_ARG() (0)
-#endif
-// rc_xattn_kernel keeps its switches as RUN-TIME branches on the (always zero, C entry checked) dbg word: with them compiled out hipcc's allocator spills
+// rc_xattn_kernel keeps its timing switches as RUN-TIME branches on the (always zero, C entry checked) dbg word: with them compiled out hipcc's allocator spills
 // 99-111 VGPRs in the image-token instances (448 B scratch; profiles/r6_kernel_resources.json gate) — the branches are scheduling fences it relies on.
 #define RC_DBG_RT(bit) ((p.dbg & (bit)) != 0)
 
@@ -52,7 +43,6 @@ struct RcLinearParams {
   long M;
   int N, K;
   float ln_eps;
-  int dbg;            // dev timing experiments (variant >> 8): 1 no stores, 2 no chunk DMA after the first, 4 no barrier, 8 no MFMA loop
   long c_dup;         // tg_rc_linear_dup: every output row is stored again c_dup elements further on, 0 = off
 };
 
@@ -123,11 +113,11 @@ template <typename V8> __device__ __forceinline__ void quad_transpose(V8& p0, V8
   p0 = __builtin_bit_cast(V8, o0); p1 = __builtin_bit_cast(V8, o1); p2 = __builtin_bit_cast(V8, o2); p3 = __builtin_bit_cast(V8, o3);
 }
 
-// KS = K / 16 k-steps (20: K = 320), NW waves per workgroup, NBUF chunk buffers in LDS, PD = fragment read-ahead in k-steps (0: the
-// compiler's own schedule).  A chunk in memory = 2 KS KiB of weight fragments + one 1-KiB vector page (v[64] fp32, u[64] fp32, pad).
-template <typename T, int KS, int NW, int NBUF, bool LN, int PD>
+// KS = K / 16 k-steps (20: K = 320), NW waves per workgroup.  A chunk in memory = 2 KS KiB of weight fragments + one 1-KiB vector page (v[64] fp32, u[64] fp32, pad).
+template <typename T, int KS, int NW, bool LN>
 __global__ __launch_bounds__(NW * 64) void rc_linear_kernel(RcLinearParams p) {
   typedef typename Vec<T>::v8 V8;
+  constexpr int NBUF = 2;               // chunk buffers in LDS
   constexpr int NP = 2 * KS + 1;        // 1-KiB DMA pieces per chunk
   constexpr int CB = NP * 1024;         // bytes of a chunk
   constexpr int PPW = (NP + NW - 1) / NW;
@@ -163,6 +153,7 @@ __global__ __launch_bounds__(NW * 64) void rc_linear_kernel(RcLinearParams p) {
                                          (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
     }
   };
+  // (a loop of one iteration: written as a plain `if`, hipcc schedules the prologue differently and every instance grows by 9 - 12 instructions)
 #pragma unroll
   for (int b = 0; b < NBUF - 1; ++b)
     if (b < NC) issue_chunk(b, b);
@@ -215,9 +206,9 @@ __global__ __launch_bounds__(NW * 64) void rc_linear_kernel(RcLinearParams p) {
     const int buf = c % NBUF;
     // chunk c has landed (this wave's pieces; the barrier covers the other waves') and every wave is done with chunk c - 1's buffer
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!RC_DBG(4)) __builtin_amdgcn_s_barrier();
-    if (c + NBUF - 1 < NC && !RC_DBG(2)) issue_chunk(c + NBUF - 1, (c + NBUF - 1) % NBUF);
-    if (pend_ch >= 0 && !RC_DBG(1)) {
+    __builtin_amdgcn_s_barrier();
+    if (c + NBUF - 1 < NC) issue_chunk(c + NBUF - 1, (c + NBUF - 1) % NBUF);
+    if (pend_ch >= 0) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         if (mok[i]) *reinterpret_cast<V8*>(outp + mrow[i] * p.ldc + pend_ch + 8 * qb) = pend[i];
@@ -255,33 +246,12 @@ __global__ __launch_bounds__(NW * 64) void rc_linear_kernel(RcLinearParams p) {
         }
     }
     const char* cb = cbase + lane * 16;
-    if RC_DBG(8) {
-    } else if constexpr (PD == 0) {
 #pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        const V8 a0 = *reinterpret_cast<const V8*>(cb + s * 1024);
-        const V8 a1 = *reinterpret_cast<const V8*>(cb + (KS + s) * 1024);
-        acc[0] = mfma32(a0, B[s], acc[0]);
-        acc[1] = mfma32(a1, B[s], acc[1]);
-      }
-    } else {
-      V8 a0[KS], a1[KS];
-#pragma unroll
-      for (int s = 0; s < PD; ++s) {
-        a0[s] = *reinterpret_cast<const V8*>(cb + s * 1024);
-        a1[s] = *reinterpret_cast<const V8*>(cb + (KS + s) * 1024);
-      }
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        if (s + PD < KS) {
-          a0[s + PD] = *reinterpret_cast<const V8*>(cb + (s + PD) * 1024);
-          a1[s + PD] = *reinterpret_cast<const V8*>(cb + (KS + s + PD) * 1024);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        acc[0] = mfma32(a0[s], B[s], acc[0]);
-        acc[1] = mfma32(a1[s], B[s], acc[1]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+    for (int s = 0; s < KS; ++s) {
+      const V8 a0 = *reinterpret_cast<const V8*>(cb + s * 1024);
+      const V8 a1 = *reinterpret_cast<const V8*>(cb + (KS + s) * 1024);
+      acc[0] = mfma32(a0, B[s], acc[0]);
+      acc[1] = mfma32(a1, B[s], acc[1]);
     }
     // epilogue: accumulator register rho of tile uu = channel ch0 + 16 uu + rho
     float o[32];
@@ -347,7 +317,7 @@ struct RcXattnParams {
   int rows_per_batch;   // tokens per batch item (multiple of 32 * NW)
   float ln_eps;
   const float* ip_scale;  // device scalar (IPAttnProcessor.scale) or NULL (1.0)
-  int dbg;                // dev timing switches (text_len >> 8): 1 no to_q MFMAs, 2 no attention, 4 no to_out MFMAs, 8 no stage DMA, 16 no barriers
+  int dbg;                // always 0 (RC_DBG_RT): 1 no to_q MFMAs, 2 no attention, 4 no to_out MFMAs, 8 no stage DMA, 16 no barriers
 };
 
 template <typename T> __device__ __forceinline__ typename Vec<T>::v8 pack8r(const f32x16& a, int r0) {
@@ -786,16 +756,14 @@ struct RcFrontParams {
   long M;
   int rows_per_batch;
   float ln_eps;
-  int dbg;                // dev timing switches: 1 no V^T stores, 2 no Q | K stores, 4 no y stores
 };
 
-// NW = 4: two 128-token workgroups per CU, ring of 3 stages (fetched 2 ahead);  NW = 8 (dev A/B): one 256-token workgroup per CU — every fetched
-// weight byte serves twice the tokens (half the LDS-DMA issue work per wave) —, ring of 4 stages (fetched 3 ahead)
+// NW = 4: two 128-token workgroups per CU, ring of 3 stages (fetched 2 ahead)
 template <typename T, int NW>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void rc_front_kernel(RcFrontParams p) {
   typedef typename Vec<T>::v8 V8;
   constexpr int KS = 20, NST = 40;
-  constexpr int DEPTH = NW == 8 ? 3 : 2, NSLOT = DEPTH + 1, PPW = 24 / NW;
+  constexpr int DEPTH = 2, NSLOT = DEPTH + 1, PPW = 24 / NW;
   constexpr int TBW = (KS + 1) * 1024, SLOT = 24 * 1024;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -827,7 +795,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   };
   issue_stage(0);
   issue_stage(1);
-  if (DEPTH == 3) issue_stage(2);
 
   // rows -> registers, GroupNorm applied in place (fp32 x * a + d, one rounding), B-operand layout
   V8 X[KS];
@@ -886,7 +853,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   V8 pend[4];
   auto flush = [&](int k) __attribute__((always_inline)) {      // the stores of stage k
     if (k < 0 || n_stores(k) == 0) return;
-    if ((k >= 30 && RC_DBG(1)) || (k < 30 && RC_DBG(2))) return;
     if (k < 30) {
       T* base = reinterpret_cast<T*>(p.qk);
       asm volatile("" : "+s"(base));
@@ -996,7 +962,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     }
   };
   auto y_chunk_store = [&](int c) __attribute__((always_inline)) {
-    if RC_DBG(4) return;
     V8 t0 = Y[4 * c], t1 = Y[4 * c + 1], t2 = Y[4 * c + 2], t3 = Y[4 * c + 3];
     quad_transpose(t0, t1, t2, t3);
     T* base = reinterpret_cast<T*>(p.y);
@@ -1050,19 +1015,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
 template <typename T>
 int launch_rc_front(const tg_rc_front_desc* d, const RcFrontParams& p, hipStream_t st) {
-  if ((d->dbg & 256) && d->rows_per_batch % 256 == 0) {      // dev A/B: one 8-wave workgroup per CU
-    const size_t lds = 4 * 24 * 1024 + 2560;
-    auto k = rc_front_kernel<T, 8>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)attr;
-    hipLaunchKernelGGL(k, dim3((unsigned)((d->M + 255) / 256)), dim3(512), lds, st, p);
-  } else {
-    const size_t lds = 3 * 24 * 1024 + 2560;
-    auto k = rc_front_kernel<T, 4>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)attr;
-    hipLaunchKernelGGL(k, dim3((unsigned)((d->M + 127) / 128)), dim3(256), lds, st, p);
-  }
+  const size_t lds = 3 * 24 * 1024 + 2560;
+  auto k = rc_front_kernel<T, 4>;
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)attr;
+  hipLaunchKernelGGL(k, dim3((unsigned)((d->M + 127) / 128)), dim3(256), lds, st, p);
   TG_LAUNCH_CHECK();
   return TG_OK;
 }
@@ -1101,11 +1058,9 @@ struct RcFfParams {
   long M;
   int n_slices;         // inner / 32, even, >= 2
   float ln_eps;
-  int dbg;              // dev timing switches: 1 no proj MFMAs, 2 no GEGLU arithmetic, 4 no net.2 MFMAs (the descriptor's TG_RC_FF_TWO_WAVE selector bit is
-                        // masked out by the C entry: it chooses the kernel on the host and never reaches one)
 };
 
-template <typename T, bool PROJ, int DBG = 0>
+template <typename T, bool PROJ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void rc_ff_kernel(RcFfParams p) {
   typedef typename Vec<T>::v8 V8;
   constexpr int KS = 20, NW = 4;
@@ -1207,9 +1162,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr int PAR = decltype(par_c)::value;
     constexpr bool F1 = decltype(f1_c)::value, GG = decltype(gg_c)::value, F2 = decltype(f2_c)::value;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!RC_DBG(16)) __builtin_amdgcn_s_barrier();
-    if (j + 1 < NS && !RC_DBG(8)) issue_w1(j + 1);
-    if (j >= 1 && j - 1 < NS && !RC_DBG(8)) issue_w2(j - 1);
+    __builtin_amdgcn_s_barrier();
+    if (j + 1 < NS) issue_w1(j + 1);
+    if (j >= 1 && j - 1 < NS) issue_w2(j - 1);
     const char* w1b = smem + PAR * W1SLOT + lane * 16;
     const char* w2b = smem + W2OFF + PAR * W2B + lane * 16;
     if constexpr (F1) {
@@ -1314,13 +1269,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   using Ff = std::false_type;
   iteration(0, C0{}, Tt{}, Ff{}, Ff{});
   iteration(1, C1{}, Tt{}, Tt{}, Ff{});
-  // (DBG: dev timing instantiations with one part of the steady-state stream compiled out: 1 no proj MFMAs, 2 no GEGLU, 4 no net.2 MFMAs)
-  using D1 = std::integral_constant<bool, !(DBG & 1)>;
-  using D2 = std::integral_constant<bool, !(DBG & 2)>;
-  using D4 = std::integral_constant<bool, !(DBG & 4)>;
   for (int j = 2; j < NS; j += 2) {
-    iteration(j, C0{}, D1{}, D2{}, D4{});
-    iteration(j + 1, C1{}, D1{}, D2{}, D4{});
+    iteration(j, C0{}, Tt{}, Tt{}, Tt{});
+    iteration(j + 1, C1{}, Tt{}, Tt{}, Tt{});
   }
   iteration(NS, C0{}, Ff{}, Tt{}, Tt{});
   iteration(NS + 1, C1{}, Ff{}, Ff{}, Tt{});
@@ -1767,8 +1718,6 @@ template <typename T>
 int launch_rc_ff(const tg_rc_ff_desc* d, const RcFfParams& p, hipStream_t st) {
   const size_t lds = 2 * 44 * 1024 + 2 * 20 * 1024;
   const long grid = (d->M + 127) / 128;
-  // (the DBG instantiations of rc_ff_kernel — parts of the steady-state stream compiled out — were dev timing aids: numbers in
-  // profiles/r4_rowchain_findings.md)
   const bool two = (d->dbg & TG_RC_FF_TWO_WAVE) != 0;      // streams of pack_ff2 / pack_po2
   if (d->wpo != nullptr) {
     if (two) launch_rc_ff_kernel<rc_ff2_kernel<T, true>>(grid, 512, lds, st, p);
@@ -1781,44 +1730,25 @@ int launch_rc_ff(const tg_rc_ff_desc* d, const RcFfParams& p, hipStream_t st) {
   return TG_OK;
 }
 
-template <typename T, int KS, int NW, int NBUF, int PD>
+// one 8-wave workgroup per CU, two chunk buffers
+template <typename T>
 int launch_rc_linear(const tg_rc_linear_desc* d, const RcLinearParams& p, hipStream_t st) {
-  const size_t lds = (size_t)NBUF * (2 * KS + 1) * 1024;
+  constexpr int KS = 20, NW = 8;
+  const size_t lds = (size_t)2 * (2 * KS + 1) * 1024;
   const long grid = (d->M + NW * 32 - 1) / (NW * 32);
   if (d->ln) {
-    auto k = rc_linear_kernel<T, KS, NW, NBUF, true, PD>;
+    auto k = rc_linear_kernel<T, KS, NW, true>;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)attr;
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NW * 64), lds, st, p);
   } else {
-    auto k = rc_linear_kernel<T, KS, NW, NBUF, false, PD>;
+    auto k = rc_linear_kernel<T, KS, NW, false>;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)attr;
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NW * 64), lds, st, p);
   }
   TG_LAUNCH_CHECK();
   return TG_OK;
-}
-
-template <typename T>
-int dispatch_rc_linear(const tg_rc_linear_desc* d, const RcLinearParams& p, hipStream_t st) {
-  switch (d->variant & 255) {
-    case 1: return launch_rc_linear<T, 20, 8, 2, 4>(d, p, st);       // pinned fragment read-ahead of 4 k-steps
-    case 2: return launch_rc_linear<T, 20, 8, 3, 0>(d, p, st);       // three chunk buffers
-    case 3: return launch_rc_linear<T, 20, 8, 3, 4>(d, p, st);
-    default: return launch_rc_linear<T, 20, 8, 2, 0>(d, p, st);      // one 8-wave workgroup per CU, the compiler's schedule
-  }
-}
-
-// The dbg switches of the kernels above (timing experiments: skip stores / barriers / MFMAs — WRONG results by design) ride in descriptor bits the
-// release path never sets; a descriptor that carries them is rejected unless the process opted in with TG_RC_DEV=1 (scripts/dev_rc_*.py) — ADVICE r4
-inline bool rc_dev_enabled() {
-#ifdef TG_RC_DEV_BUILD
-  static const bool on = []() { const char* e = getenv("TG_RC_DEV"); return e != nullptr && e[0] == '1'; }();
-  return on;
-#else
-  return false;          // release build: the switches are not compiled into the kernels (RC_DBG above)
-#endif
 }
 
 }  // namespace
@@ -1830,34 +1760,33 @@ extern "C" int tg_rc_linear_dup(const tg_rc_linear_desc* d, int64_t c_dup_offset
   TG_CHECK(d->dtype == TG_BF16 || d->dtype == TG_F16, TG_ERR_ARG, "tg_rc_linear: dtype %d", d->dtype);
   TG_CHECK(d->K == 320, TG_ERR_ARG, "tg_rc_linear: K = %d (320: the token row lives in registers; the K = 640 variant of round 4 was removed)", d->K);
   TG_CHECK(d->N > 0 && d->N % 64 == 0, TG_ERR_ARG, "tg_rc_linear: N = %d must be a positive multiple of 64", d->N);
-  TG_CHECK(d->variant >= 0 && ((d->variant >> 8) == 0 || rc_dev_enabled()), TG_ERR_ARG, "tg_rc_linear: variant %d carries dev bits (TG_RC_DEV=1 enables them)", d->variant);
+  TG_CHECK(d->variant == 0, TG_ERR_ARG, "tg_rc_linear: variant = %d (reserved, must be 0)", d->variant);
   TG_CHECK(d->M > 0 && d->x && d->wpk && d->out, TG_ERR_ARG, "tg_rc_linear: null operand or M <= 0");
   TG_CHECK(d->ldx >= d->K && d->ldx % 8 == 0 && d->ldc >= d->N && d->ldc % 8 == 0, TG_ERR_ARG, "tg_rc_linear: row pitches must be multiples of 8 elements");
   TG_CHECK(!d->res || (d->ldres >= d->N && d->ldres % 8 == 0), TG_ERR_ARG, "tg_rc_linear: residual pitch");
   TG_CHECK(c_dup_offset == 0 || (c_dup_offset % 8 == 0 && c_dup_offset >= (d->M - 1) * d->ldc + d->N), TG_ERR_ARG,
            "tg_rc_linear_dup: c_dup_offset = %lld must be a multiple of 8 elements past the first destination", (long long)c_dup_offset);
-    RcLinearParams p;
+  RcLinearParams p;
   p.c_dup = (long)c_dup_offset;
   p.x = d->x; p.ldx = d->ldx; p.wpk = d->wpk; p.res = d->res; p.ldres = d->ldres;
-  p.out = d->out; p.ldc = d->ldc; p.M = d->M; p.N = d->N; p.K = d->K; p.ln_eps = d->ln_eps; p.dbg = d->variant >> 8;
+  p.out = d->out; p.ldc = d->ldc; p.M = d->M; p.N = d->N; p.K = d->K; p.ln_eps = d->ln_eps;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->dtype == TG_BF16) return dispatch_rc_linear<bf16_t>(d, p, st);
-  return dispatch_rc_linear<f16_t>(d, p, st);
+  if (d->dtype == TG_BF16) return launch_rc_linear<bf16_t>(d, p, st);
+  return launch_rc_linear<f16_t>(d, p, st);
 }
 
 extern "C" int tg_rc_xattn(const tg_rc_xattn_desc* d, void* stream) {
   TG_CHECK(d != nullptr, TG_ERR_ARG, "tg_rc_xattn: null descriptor");
   TG_CHECK(d->dtype == TG_BF16 || d->dtype == TG_F16, TG_ERR_ARG, "tg_rc_xattn: dtype %d", d->dtype);
   TG_CHECK(d->h && d->wq && d->kv && d->wo && d->out && d->M > 0, TG_ERR_ARG, "tg_rc_xattn: null operand or M <= 0");
-  TG_CHECK(d->text_len == 77 || (rc_dev_enabled() && d->text_len > 0 && (d->text_len & 255) == 77), TG_ERR_ARG,
-           "tg_rc_xattn: %d text keys (built for CLIP's 77; the high bits are dev switches, TG_RC_DEV=1)", d->text_len);
+  TG_CHECK(d->text_len == 77, TG_ERR_ARG, "tg_rc_xattn: %d text keys (built for CLIP's 77)", d->text_len);
   TG_CHECK(d->ip_tokens == 0 || d->ip_tokens == 4 || d->ip_tokens == 16, TG_ERR_ARG, "tg_rc_xattn: %d image tokens (0, 4 or 16)", d->ip_tokens);
   TG_CHECK(d->rows_per_batch > 0 && d->rows_per_batch % 128 == 0 && d->M % d->rows_per_batch == 0, TG_ERR_ARG,
            "tg_rc_xattn: rows_per_batch = %d must be a multiple of 128 that divides M (a workgroup's 128 tokens share one key set)", d->rows_per_batch);
   TG_CHECK(d->ldh >= 320 && d->ldh % 8 == 0 && d->ldc >= 320 && d->ldc % 8 == 0, TG_ERR_ARG, "tg_rc_xattn: row pitches");
   RcXattnParams p;
   p.h = d->h; p.ldh = d->ldh; p.wq = d->wq; p.kv = d->kv; p.wo = d->wo; p.out = d->out; p.ldc = d->ldc; p.M = d->M;
-  p.rows_per_batch = d->rows_per_batch; p.ln_eps = d->ln_eps; p.ip_scale = d->ip_scale; p.dbg = d->text_len >> 8;
+  p.rows_per_batch = d->rows_per_batch; p.ln_eps = d->ln_eps; p.ip_scale = d->ip_scale; p.dbg = 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (d->dtype == TG_BF16) return dispatch_rc_xattn<bf16_t>(d, p, st);
   return dispatch_rc_xattn<f16_t>(d, p, st);
@@ -1888,10 +1817,10 @@ extern "C" int tg_rc_ff(const tg_rc_ff_desc* d, void* stream) {
   TG_CHECK(d->inner >= 64 && d->inner % 64 == 0, TG_ERR_ARG, "tg_rc_ff: inner = %d must be a multiple of 64", d->inner);
   TG_CHECK(d->ldh >= 320 && d->ldh % 8 == 0 && d->ldc >= 320 && d->ldc % 8 == 0, TG_ERR_ARG, "tg_rc_ff: row pitches");
   TG_CHECK(!d->wpo || (d->res0 && d->ldres >= 320 && d->ldres % 8 == 0), TG_ERR_ARG, "tg_rc_ff: proj_out needs its residual");
-  TG_CHECK((d->dbg & ~TG_RC_FF_TWO_WAVE) == 0 || rc_dev_enabled(), TG_ERR_ARG, "tg_rc_ff: dbg = %d (dev switches need TG_RC_DEV=1)", d->dbg);
+  TG_CHECK((d->dbg & ~TG_RC_FF_TWO_WAVE) == 0, TG_ERR_ARG, "tg_rc_ff: dbg = %d (TG_RC_FF_TWO_WAVE is its only bit, the rest is reserved)", d->dbg);
   RcFfParams p;
   p.h = d->h; p.ldh = d->ldh; p.w1 = d->w1; p.w2 = d->w2; p.b2 = d->b2; p.wpo = d->wpo; p.res0 = d->res0; p.ldres = d->ldres;
-  p.out = d->out; p.ldc = d->ldc; p.M = d->M; p.n_slices = d->inner / 32; p.ln_eps = d->ln_eps; p.dbg = d->dbg & ~TG_RC_FF_TWO_WAVE;
+  p.out = d->out; p.ldc = d->ldc; p.M = d->M; p.n_slices = d->inner / 32; p.ln_eps = d->ln_eps;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (d->dtype == TG_BF16) return launch_rc_ff<bf16_t>(d, p, st);
   return launch_rc_ff<f16_t>(d, p, st);
@@ -1905,10 +1834,10 @@ extern "C" int tg_rc_front(const tg_rc_front_desc* d, void* stream) {
            "tg_rc_front: rows_per_batch = %d must be a multiple of 128 that divides M", d->rows_per_batch);
   TG_CHECK(d->ldx >= 320 && d->ldx % 8 == 0 && d->ldy >= 320 && d->ldy % 8 == 0 && d->ldqk >= 640 && d->ldqk % 8 == 0 && d->ldt >= d->rows_per_batch,
            TG_ERR_ARG, "tg_rc_front: row pitches");
-  TG_CHECK(d->dbg == 0 || rc_dev_enabled(), TG_ERR_ARG, "tg_rc_front: dbg = %d (dev switches need TG_RC_DEV=1)", d->dbg);
+  TG_CHECK(d->dbg == 0, TG_ERR_ARG, "tg_rc_front: dbg = %d (reserved, must be 0)", d->dbg);
   RcFrontParams p;
   p.x = d->x; p.ldx = d->ldx; p.coef = d->coef; p.win = d->win; p.wqkv = d->wqkv; p.y = d->y; p.ldy = d->ldy; p.qk = d->qk; p.ldqk = d->ldqk;
-  p.vt = d->vt; p.ldt = d->ldt; p.M = d->M; p.rows_per_batch = d->rows_per_batch; p.ln_eps = d->ln_eps; p.dbg = d->dbg;
+  p.vt = d->vt; p.ldt = d->ldt; p.M = d->M; p.rows_per_batch = d->rows_per_batch; p.ln_eps = d->ln_eps;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (d->dtype == TG_BF16) return launch_rc_front<bf16_t>(d, p, st);
   return launch_rc_front<f16_t>(d, p, st);

@@ -218,10 +218,11 @@ def dup_rows(src, dst):
     return dst
 
 
-def rc_linear(x, wpk, N, *, res=None, ln_eps=None, out=None, variant=0, pair_out=None):
+def rc_linear(x, wpk, N, *, res=None, ln_eps=None, out=None, pair_out=None, _reserved=0):
     """Row-chain projection (csrc/tg_rowchain.hip): out = [LayerNorm-folded] x @ W^T + v (+ res) with the token rows in registers;
     ``wpk`` = ``weights_pack.rc_pack(W, v, u)`` (uint8 chunk stream), x [M, 320].  ``pair_out`` (dense [2 M, N]): both halves receive the
-    result from the kernel's epilogue (``tg_rc_linear_dup``); returns ``pair_out[:M]``."""
+    result from the kernel's epilogue (``tg_rc_linear_dup``); returns ``pair_out[:M]``.  ``_reserved``: the descriptor's reserved word (the entry refuses
+    anything but 0; the refusal test sets it)."""
     from ._lib import RcLinearDesc
     _need_cuda(x)
     M, K = x.shape
@@ -243,7 +244,7 @@ def rc_linear(x, wpk, N, *, res=None, ln_eps=None, out=None, variant=0, pair_out
     d.out, d.ldc = _ptr(out), int(out.stride(0))
     d.M, d.N, d.K = int(M), int(N), int(K)
     d.ln, d.ln_eps = (1, float(ln_eps)) if ln_eps is not None else (0, 0.0)
-    d.variant = int(variant)
+    d.variant = int(_reserved)
     _profiled(lambda: _lib.check(_lib.lib().tg_rc_linear_dup(C.byref(d), dup, _stream()) if dup else _lib.lib().tg_rc_linear(C.byref(d), _stream())),
               "rc_linear_kernel<320>" + ("+ln" if ln_eps is not None else ""),
               M, N, K, 2.0 * M * N * K, res is not None)
@@ -324,9 +325,9 @@ def rc_xattn(h, wq, kv, wo, rows_per_batch, ln_eps, ip_tokens, ip_scale=None, ou
     return out
 
 
-def rc_ff(h, w1, w2, b2, inner, ln_eps, wpo=None, res0=None, out=None, dbg=0, two_wave=False):
+def rc_ff(h, w1, w2, b2, inner, ln_eps, wpo=None, res0=None, out=None, two_wave=False, _reserved=0):
     """norm3 + GEGLU feed-forward + residual (+ proj_out + its residual) in one launch; see tg_rc_ff.  ``two_wave``: the streams are
-    ``rowchain.pack_ff2`` / ``pack_po2`` and the launch is ``rc_ff2_kernel`` (two waves per SIMD)"""
+    ``rowchain.pack_ff2`` / ``pack_po2`` and the launch is ``rc_ff2_kernel`` (two waves per SIMD).  ``_reserved``: as in ``rc_linear``"""
     from ._lib import RcFfDesc
     _need_cuda(h)
     M, Cc = h.shape
@@ -339,7 +340,7 @@ def rc_ff(h, w1, w2, b2, inner, ln_eps, wpo=None, res0=None, out=None, dbg=0, tw
     d.w1, d.w2, d.b2, d.wpo = _ptr(w1), _ptr(w2), _ptr(b2), _ptr(wpo)
     d.res0, d.ldres = (_ptr(res0), int(res0.stride(0))) if res0 is not None else (None, 0)
     d.out, d.ldc = _ptr(out), int(out.stride(0))
-    d.M, d.inner, d.ln_eps, d.dbg = int(M), int(inner), float(ln_eps), int(dbg) | (_lib.RC_FF_TWO_WAVE if two_wave else 0)
+    d.M, d.inner, d.ln_eps, d.dbg = int(M), int(inner), float(ln_eps), int(_reserved) | (_lib.RC_FF_TWO_WAVE if two_wave else 0)
     fl = 2.0 * M * 320 * (3 * int(inner)) + (2.0 * M * 320 * 320 if wpo is not None else 0.0)
     _profiled(lambda: _lib.check(_lib.lib().tg_rc_ff(C.byref(d), _stream())), ("rc_ff2_kernel<320>" if two_wave else "rc_ff_kernel<320>") + ("+proj_out" if wpo is not None else ""),
               M, 320, 3 * int(inner), fl, True,
@@ -347,8 +348,8 @@ def rc_ff(h, w1, w2, b2, inner, ln_eps, wpo=None, res0=None, out=None, dbg=0, tw
     return out
 
 
-def rc_front(x, coef, win, wqkv, rows_per_batch, ln_eps, y=None, qk=None, vt=None, dbg=0):
-    """GroupNorm (coefficients) + proj_in + LayerNorm1 + q | k | v in one launch; see tg_rc_front.  Returns (y, qk, vt, ldt)."""
+def rc_front(x, coef, win, wqkv, rows_per_batch, ln_eps, y=None, qk=None, vt=None, _reserved=0):
+    """GroupNorm (coefficients) + proj_in + LayerNorm1 + q | k | v in one launch; see tg_rc_front.  Returns (y, qk, vt, ldt).  ``_reserved``: as in ``rc_linear``"""
     from ._lib import RcFrontDesc
     _need_cuda(x)
     M, Cc = x.shape
@@ -365,7 +366,7 @@ def rc_front(x, coef, win, wqkv, rows_per_batch, ln_eps, y=None, qk=None, vt=Non
     d.dtype = _dt(x)
     d.x, d.ldx, d.coef, d.win, d.wqkv = _ptr(x), int(x.stride(0)), _ptr(coef), _ptr(win), _ptr(wqkv)
     d.y, d.ldy, d.qk, d.ldqk, d.vt, d.ldt = _ptr(y), int(y.stride(0)), _ptr(qk), int(qk.stride(0)), _ptr(vt), int(vt.stride(1))
-    d.M, d.rows_per_batch, d.ln_eps, d.dbg = int(M), int(rows_per_batch), float(ln_eps), int(dbg)
+    d.M, d.rows_per_batch, d.ln_eps, d.dbg = int(M), int(rows_per_batch), float(ln_eps), int(_reserved)
     fl = 2.0 * M * 320 * (320 + 960)
     _profiled(lambda: _lib.check(_lib.lib().tg_rc_front(C.byref(d), _stream())), "rc_front_kernel<320>", M, 960, 320, fl, False,
               alg_bytes=2.0 * (5 * M * 320 + 4 * 320 * 320))

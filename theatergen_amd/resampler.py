@@ -224,7 +224,7 @@ class Resampler(nn.Module):
         if side is None or side.device != dev:
             side = self._side = torch.cuda.Stream(device=dev)
         self.layers[0][0].kv_image(xp, b, L, kvs[0][0], kvs[0][1], ldt)
-        use_side = len(self.layers) > 1 and os.environ.get("TG_RESAMPLER_SIDE", "1") == "1"
+        use_side = len(self.layers) > 1
         if use_side:
             side.wait_stream(cur)
             with torch.cuda.stream(side):

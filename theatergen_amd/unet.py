@@ -31,7 +31,7 @@ from . import rowchain
 from .attention_processor import (tensor_version, Attention, AttnProcessor, CNAttnProcessor, IPAttnProcessor, _cached, front_eligible, fused_cross_block,
                                   ln_weight, pair_output, self_attention_from_qkv)
 from .config import UNetConfig
-from .weights_pack import pack_conv1x1, pack_conv3x3, pack_conv3x3_up2, pack_geglu, pack_ln_linear, rc_pack_tiles
+from .weights_pack import pack_conv1x1, pack_conv3x3, pack_conv3x3_up2, pack_geglu, rc_pack_tiles
 
 
 class DeviceSchedule:
@@ -71,8 +71,6 @@ class _Packed:
         return hit[1]
 
 
-# dev switch: TG_NO_GN_FUSE=1 keeps GroupNorm and conv two ops everywhere (A/B of the fused window staging)
-_FUSE_GN = not os.environ.get("TG_NO_GN_FUSE")
 # round 6: the statistics pass of a GroupNorm whose input is a slab conv's output (ResnetBlock2D.norm2 after conv1, Transformer2DModel.norm after conv2) comes
 # out of that conv's epilogue as partial sums (tg_gemm_desc.out_gn_partials) where the two-wave slab kernel runs the layer unsplit.  TG_GN_EPI=0 (dev A/B) = off.
 _GN_EPI = os.environ.get("TG_GN_EPI", "1") != "0"
@@ -80,19 +78,10 @@ _GN_EPI = os.environ.get("TG_GN_EPI", "1") != "0"
 
 def _gn_of(gn, groups):
     return gn if gn is not None and "partials" in gn and gn["groups"] == groups else None
-# dev switch: TG_NO_LN_FUSE=1 keeps LayerNorm a launch of its own in front of the q|k|v / to_q / GEGLU projections
-# TG_LN_MODE bits: 1 = fold norm1 / norm2 into attn1 q|k|v / attn2.to_q, 2 = fold norm3 into the GEGLU GEMM, 4 = row statistics from a
-# statistics-only pass (tg_layernorm_stats) instead of inside the GEMM.  0 = LayerNorm launches (round 2).
-# Default 1, by same-box graph-replay A/B (profiles/r3_ln_findings.md): attention-only fold with in-kernel statistics +1.06 % images/s;
-# folding norm3 too costs the FeedForward its 256 x 256 big-tile GEGLU kernel (-0.4 % overall); a separate statistics pass is slower
-# than taking them from the staged tiles (+0.75 % instead of +1.06 %).
-_LN_MODE = 0 if os.environ.get("TG_NO_LN_FUSE") else int(os.environ.get("TG_LN_MODE", "1"))
-# norm3 folded into the GEGLU GEMM for row counts up to this (0 = never): where the plain GEGLU GEMM runs on the 128 x 128 kernel anyway (not the 256 x 256 big tile of
-# the 32 x 32 level) the fold costs no tile choice and removes the layernorm launch
-_LN_FF_MAX_ROWS = int(os.environ.get("TG_LN_FF_MAX_ROWS", "0"))
-_CONV_OUT_GN = os.environ.get("TG_CONV_OUT_GN", "1") != "0"      # dev A/B knob: 0 = GroupNorm apply launch + conv_out
-_FF_PAD = os.environ.get("TG_FF_PAD", "1") != "0"      # round 5: pad the FeedForward hidden tensor's / net.2 weight's row pitch (see FeedForward._hidden)
 
+
+# LayerNorm: norm1 / norm2 are folded into attn1 q|k|v / attn2.to_q with in-kernel row statistics; norm3 stays a launch, so the FeedForward keeps
+# its 256 x 256 big-tile GEGLU kernel (same-box graph-replay A/B of the alternatives: profiles/r3_ln_findings.md)
 _FUSE_LN_MIN_ROWS = int(os.environ.get("TG_LN_FUSE_MIN_ROWS", "2048"))     # below: few 128-row tiles, the 64 x 64-tile path wins
 
 
@@ -132,11 +121,11 @@ class ResnetBlock2D(nn.Module):
         if tproj is not None:
             off, width = self.temb_slot
             kw1.update(bvec=tproj[:, off:off + width], rows_per_batch=x.hw)
-        fuse2 = _FUSE_GN and ops.conv3x3_takes_gn(x.t.dtype, x.b, x.h, x.w, self.out_channels, 0, self.out_channels)
+        fuse2 = ops.conv3x3_takes_gn(x.t.dtype, x.b, x.h, x.w, self.out_channels, 0, self.out_channels)
         gn1 = {"groups": self.groups} if _GN_EPI and fuse2 else None      # conv1 -> norm2: the coefficients are all norm2 needs
         if gn1 is not None:
             kw1.update(gn_out=gn1)
-        if _FUSE_GN and ops.conv3x3_takes_gn(x.t.dtype, x.b, x.h, x.w, x.c, c1, self.out_channels):
+        if ops.conv3x3_takes_gn(x.t.dtype, x.b, x.h, x.w, x.c, c1, self.out_channels):
             g0 = _gn_of(x.gn, self.groups) if skip is None else None
             if g0 is not None:
                 coef = ops.groupnorm_from_partials(g0, x.b, x.hw, x.c, self.eps, self.norm1.weight, self.norm1.bias)
@@ -261,15 +250,15 @@ class FeedForward(nn.Module):
     def _hidden(self, M, inner, like):
         """the [M, inner] hidden tensor.  Round 5: when its row pitch would be a multiple of 1 KiB (inner = 2560 / 5120: the 32 x 32 / 16 x 16 levels) the rows are
         padded by 64 elements (and net.2's weight likewise, ``_w2``) — its only consumers are the two FeedForward GEMMs, and the lockstep workgroups of those
-        single-round launches otherwise crowd a few L2 channels (profiles/r5_operand_pitch.txt); TG_FF_PAD=0 switches it off"""
-        if _FF_PAD and inner % 512 == 0:
+        single-round launches otherwise crowd a few L2 channels (profiles/r5_operand_pitch.txt)"""
+        if inner % 512 == 0:
             return torch.empty((M, inner + 64), dtype=like.dtype, device=like.device)[:, :inner]
         return torch.empty((M, inner), dtype=like.dtype, device=like.device)
 
     def _w2(self):
         w2 = self.net[2].weight
         inner = w2.shape[1]
-        if not (_FF_PAD and inner % 512 == 0):
+        if inner % 512:
             return w2
 
         def build():
@@ -278,20 +267,11 @@ class FeedForward(nn.Module):
             return wp
         return self._p.get("w2pad", [w2], build)[:, :inner]
 
-    def run(self, x2d, residual, ln=None):
-        """``ln`` = (nn.LayerNorm, row statistics or None): ``x2d`` is the un-normalised stream and the norm is folded into the GEGLU GEMM"""
+    def run(self, x2d, residual):
         proj = self.net[0].proj
         M, K = x2d.shape
         inner = proj.weight.shape[0] // 2
-        if ln is not None:
-            norm, rows = ln
-
-            def build():
-                wp, bp = pack_geglu(proj.weight.detach(), proj.bias.detach())
-                return pack_ln_linear(wp, bp, norm.weight, norm.bias)
-            wl, ul, vl = self._p.get("geglu_ln", [proj.weight, proj.bias, norm.weight, norm.bias], build)
-            g = ops.gemm(x2d, wl, M, wl.shape[0], K, geglu=True, ln=(ul, vl, norm.eps, rows), out=self._hidden(M, inner, x2d))
-        elif M > 64 and inner % 32 == 0:
+        if M > 64 and inner % 32 == 0:
             # GEGLU fused into the C -> 8C GEMM epilogue: the [M, 8C] pre-activation is never written
             wp, bp = self._p.get("geglu", [proj.weight, proj.bias], lambda: pack_geglu(proj.weight.detach(), proj.bias.detach()))
             g = ops.gemm(x2d, wp, M, wp.shape[0], K, bias=bp, geglu=True, out=self._hidden(M, inner, x2d))
@@ -357,32 +337,24 @@ class BasicTransformerBlock(nn.Module):
         one = (lambda fn, t: self._attn1_pair(fn, t)) if pair else (lambda fn, t: fn())
         bf = 2 * b if pair else b
         M = 2 * M if pair else M                       # the path is chosen for the rows attn2 and the feed-forward see: the same launches as without sharing
-        if _LN_MODE and M >= _FUSE_LN_MIN_ROWS and C % 64 == 0 and x2d.stride(0) == C:
-            # LayerNorm rides in the projection that consumes it (tg_gemm ln_u / ln_v): no normalised tensor.  Row statistics: a
+        if M >= _FUSE_LN_MIN_ROWS and C % 64 == 0 and x2d.stride(0) == C:
+            # norm1 / norm2 ride in the projection that consumes them (tg_gemm ln_u / ln_v): no normalised tensor.  Row statistics: a
             # statistics-only pass (half the layernorm kernel's traffic) or taken inside the GEMM from its own A tiles
             def folded(norm, t, qkv_channels=0):
                 # round 6: where the ping-pong GEMMs take attn1's q | k | v^T projection (tg_gemm_pp.hip: they fold the LayerNorm from PRECOMPUTED row statistics;
                 # the planner says so: ops.ln_qkv_takes_stats) the statistics-only pass runs first: 16 x 16 level, 4096 x 3840 x 1280: 75 -> 54 + 6 us
-                stats = _LN_MODE & 4 or (qkv_channels and ops.ln_qkv_takes_stats(t.dtype, t.shape[0], qkv_channels, t.shape[1], n))
+                stats = qkv_channels and ops.ln_qkv_takes_stats(t.dtype, t.shape[0], qkv_channels, t.shape[1], n)
                 return (norm, ops.layernorm_stats(t, norm.eps) if stats else None)
-            if _LN_MODE & 1:
-                if pre_qkv is not None:
-                    x2d = one(lambda: self_attention_from_qkv(self.attn1, pre_qkv[0], pre_qkv[1], pre_qkv[2], b, n, x2d), x2d)
-                else:
-                    x2d = one(lambda: self._call(self.attn1, x2d, b, n, None, x2d, ca_kwargs, ln=folded(self.norm1, x2d, self.attn1.to_q.weight.shape[0])), x2d)
-                # first level of SD-1.5: norm2 + attn2 + residual as ONE row-chain launch (q, scores and O stay in registers)
-                h2 = fused_cross_block(self.attn2, self.norm2, x2d, bf, n, enc, ca_kwargs)
-                x2d = h2 if h2 is not None else self._call(self.attn2, x2d, bf, n, enc, x2d, ca_kwargs, ln=folded(self.norm2, x2d))
+            if pre_qkv is not None:
+                x2d = one(lambda: self_attention_from_qkv(self.attn1, pre_qkv[0], pre_qkv[1], pre_qkv[2], b, n, x2d), x2d)
             else:
-                h = ops.layernorm(x2d, self.norm1.weight, self.norm1.bias, self.norm1.eps)
-                x2d = one(lambda: self._call(self.attn1, h, b, n, None, x2d, ca_kwargs), x2d)
-                h = ops.layernorm(x2d, self.norm2.weight, self.norm2.bias, self.norm2.eps)
-                x2d = self._call(self.attn2, h, bf, n, enc, x2d, ca_kwargs)
+                x2d = one(lambda: self._call(self.attn1, x2d, b, n, None, x2d, ca_kwargs, ln=folded(self.norm1, x2d, self.attn1.to_q.weight.shape[0])), x2d)
+            # first level of SD-1.5: norm2 + attn2 + residual as ONE row-chain launch (q, scores and O stay in registers)
+            h2 = fused_cross_block(self.attn2, self.norm2, x2d, bf, n, enc, ca_kwargs)
+            x2d = h2 if h2 is not None else self._call(self.attn2, x2d, bf, n, enc, x2d, ca_kwargs, ln=folded(self.norm2, x2d))
             fused = self.ff.run_fused(x2d, self.norm3, tail)
             if fused is not None:
                 return (fused, True) if tail is not None else fused
-            if _LN_MODE & 2 or M <= _LN_FF_MAX_ROWS:
-                return self.ff.run(x2d, x2d, ln=folded(self.norm3, x2d))
             h = ops.layernorm(x2d, self.norm3.weight, self.norm3.bias, self.norm3.eps)
             return self.ff.run(h, x2d)
         h = ops.layernorm(x2d, self.norm1.weight, self.norm1.bias, self.norm1.eps)
@@ -423,7 +395,7 @@ class Transformer2DModel(nn.Module):
         (``tg_rc_front``; first level of SD-1.5) -> (y, Q | K, V^T, ldt), or None when the shapes / processors are not eligible."""
         blk = self.transformer_blocks[0]
         M, C = x.t.shape
-        if (not rowchain.ENABLED or not (rowchain.MODE & 8) or not _LN_MODE & 1 or C != 320 or w_in.shape != (320, 320) or M < rowchain.MIN_ROWS_CHAIN
+        if (not rowchain.ENABLED or not (rowchain.MODE & 8) or C != 320 or w_in.shape != (320, 320) or M < rowchain.MIN_ROWS_CHAIN
                 or x.hw % 128 or x.t.stride(0) != C or x.c != 320 or not front_eligible(blk.attn1, ca_kwargs)):
             return None
         g = _gn_of(x.gn, self.groups)
@@ -830,7 +802,7 @@ class UNet2DConditionModel(nn.Module):
 
         w_out = self._p.get("conv_out", [self.conv_out.weight], lambda: pack_conv3x3(self.conv_out.weight.detach()))
         odt = out_dtype if out_dtype is not None else dt
-        if _CONV_OUT_GN and ops.conv_out_takes_gn(x.t.shape[-1], x.h, x.w, cfg.out_channels):
+        if ops.conv_out_takes_gn(x.t.shape[-1], x.h, x.w, cfg.out_channels):
             # conv_norm_out + SiLU inside conv_out's window staging: statistics launch only, the normalised tensor never exists
             coef = ops.groupnorm_coef(x.t, x.b, x.hw, cfg.norm_num_groups, cfg.norm_eps, self.conv_norm_out.weight, self.conv_norm_out.bias)
             out = ops.conv_out(x.t, w_out, self.conv_out.bias, B, x.h, x.w, cfg.out_channels, odt, coef=coef, silu=True)

@@ -1,6 +1,8 @@
 """dev helper: IN-SITU per-launch times of the GEMM / conv launches of one eager CFG-batch-16 UNet step (HIP events around every
 tg_gemm launch, operands as the real call leaves them in L2 / MALL), for several TG_GEMM_FLAGS variants in ONE process,
-interleaved; prints per (kernel, shape, epilogue) the mean microseconds of each variant.
+interleaved; prints per (kernel, shape, epilogue) the mean microseconds of each variant.  Only the planner's bits of the word
+exist (8 no big tile, 128 no slab kernel, 1024 no patch tiles, 2048 / 4096 the slab split rules): a variant changes which kernel
+runs a launch, never what a kernel does.
     python scripts/dev_insitu_gemm.py "8 0" [reps]"""
 import collections
 import os

@@ -149,3 +149,73 @@ def test_layernorm_fold_with_offset_output(monkeypatch):
         out = _rows(g, M, N, ld, off)
         _, plan = _launch(monkeypatch, ops.linear, x, wp.to(DEV), ln=(u.to(DEV), v.to(DEV), 1e-5, rows), out=out)
         assert plan[3] == 6
+
+
+# ---- TG_GEMM_FLAGS is a planner knob: no bit of it reaches a kernel or a launcher ----------------------------------------------------
+# what the word once meant besides the planner's five bits: stagger (1), priority hints (2, 32768), the big tile's epilogue (4), the tile-major work
+# order (8192), the two-wave slab kernel's timing switches (1 << 16 .. 1 << 18, wrong results by design)
+RETIRED_FLAGS = 1 | 2 | 4 | 8192 | 32768 | 1 << 16 | 1 << 17 | 1 << 18
+FAMILIES = [
+    # id, kind, smallest shape of the family in LINEAR / CONV above and tests/test_round6_gpu.py's PP_SHAPES / P160_SHAPES, force_tile, kernel label
+    ("glds_128x128", "linear", (512, 320, 320), 1, "gemm_glds_kernel<plain,128x128>"),
+    ("glds_64x64", "linear", (512, 320, 320), 2, "gemm_glds_kernel<plain,64x64>"),
+    ("glds_conv", "conv", (2, 32, 32, 320, 320, 2), 0, "gemm_glds_kernel<conv,"),
+    ("halo_conv", "conv", (2, 64, 64, 320, 320, 1), 0, "conv_halo_kernel<128x128>"),
+    ("t160", "linear", (2048, 640, 640), 21, "gemm_glds_kernel<plain,128x160>"),
+    ("ln_fold", "ln", (1024, 640, 320), 0, "gemm_glds_kernel<plain+ln,"),
+    ("pingpong_24", "linear", (256, 256, 128), 24, "pp_gemm_kernel<256x256>"),
+    ("pingpong_25", "linear", (256, 160, 128), 25, "pp160_gemm_kernel<256x160>"),
+    ("big_tile_10", "linear", (512, 320, 320), 10, "bt_gemm_kernel<256x256>"),
+    ("big_tile_10_geglu", "geglu", (512, 320, 320), 10, "bt_gemm_kernel<256x256>"),      # the launch bit 2 used to move off the register-only epilogue
+    ("slab", "slab1", (2, 64, 64, 320, 320, 1), 11, "conv_slab_kernel<128x320>"),
+    ("slab_two_wave", "conv", (2, 64, 64, 320, 320, 1), 11, "conv_slab_pp_kernel<128x320>"),
+]
+
+
+@pytest.mark.parametrize("family", FAMILIES, ids=[f[0] for f in FAMILIES])
+def test_retired_flag_bits_reach_no_kernel(monkeypatch, family):
+    """one launch per kernel family with TG_GEMM_FLAGS unset and one with every retired bit set: the same kernel, the same bits out"""
+    from theatergen_amd import ops
+    from theatergen_amd.weights_pack import pack_conv3x3, pack_ln_linear
+    name, kind, shape, ft, label = family
+    g = torch.Generator().manual_seed(len(name) + ft + sum(shape))
+    if kind in ("conv", "slab1"):
+        B, H, W, cin, cout, stride = shape
+        x = _rows(g, B * H * W, cin, cin, 0)
+        wp = pack_conv3x3(torch.randn(cout, cin, 3, 3, generator=g) / math.sqrt(9 * cin)).to(BF16).to(DEV)
+        M = B * ((H - 1) // stride + 1) * ((W - 1) // stride + 1)
+        bias, res = _rows(g, 1, cout, cout, 0)[0], _rows(g, M, cout, cout, 0)
+        run = lambda: ops.conv3x3(x, wp, B, H, W, cin, stride=stride, force_tile=ft, bias=bias, res=res)
+        if kind == "slab1":
+            monkeypatch.setenv("TG_SLAB_PP", "0")                 # conv_slab_kernel on a layer the two-wave kernel takes
+    else:
+        M, N, K = shape
+        a = _rows(g, M, K, K, 0)
+        w = _rows(g, N, K, K, 0, 1 / math.sqrt(K))
+        bias = _rows(g, 1, N, N, 0)[0]
+        if kind == "ln":
+            wl, u, v = pack_ln_linear(w, bias, (1 + 0.1 * torch.randn(K, generator=g)).to(DEV), (0.1 * torch.randn(K, generator=g)).to(DEV))
+            run = lambda: ops.linear(a, wl, ln=(u, v, 1e-5))
+        elif kind == "geglu":
+            run = lambda: ops.gemm(a, w, M, N, K, bias=bias, geglu=True, force_tile=ft)
+        else:
+            res = _rows(g, M, N, N, 0)
+            run = lambda: ops.linear(a, w, bias, res=res, force_tile=ft)
+
+    def launch():
+        ops.gemm_profile_start()
+        try:
+            out = run()
+            torch.cuda.synchronize()
+        finally:
+            recs = ops.gemm_profile_stop()
+        assert len(recs) == 1 and recs[0]["kernel"].startswith(label), recs
+        return out, recs[0]["kernel"]
+    monkeypatch.delenv("TG_GEMM_FLAGS", raising=False)
+    want, kernel = launch()
+    monkeypatch.setenv("TG_GEMM_FLAGS", str(RETIRED_FLAGS))
+    got, kernel_flags = launch()
+    assert kernel_flags == kernel
+    assert bool(torch.isfinite(want.float()).all())
+    same = torch.equal(want, got)
+    assert same, f"{name}: TG_GEMM_FLAGS={RETIRED_FLAGS} changed the output of {kernel}"

@@ -39,7 +39,6 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(GemmParams p) {
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* sS = reinterpret_cast<T*>(smem);                 // [NI*8][64]   halo slab of the current channel chunk
-  stagger_first_round(p.flags, smem);
   // weight-tile ring: 3 stages (2 tiles in flight) wherever slab + 3 x 16 KB still lets two blocks share a CU (every
   // variant but the 64-wide one): a K-step's period was one DMA round trip of the next W tile, not its 16 MFMAs
   constexpr int WST = ((size_t)NI * 8 * BK + 3 * BN * BK) * sizeof(T) <= 80 * 1024 ? 3 : 2;

@@ -16,7 +16,7 @@
 //     bias / time-embedding vector / residual loads and the stores are 16 bytes per lane on whole 128-byte rows; split work items store fp32 partial tiles
 //     in tile-local order for tg_gemm.hip's fixed-order reduce.
 // (First build of the round: the two compute groups one barrier apart, tg_gemm_pp.hip's schedule — four barriers per K-step, a phase's nine reads took ~480
-// cycles against 320 of MFMA: no faster than conv_slab_kernel, scripts/dev_slab_pp.py ablations in profiles/r6_slab_findings.md.)
+// cycles against 320 of MFMA: no faster than conv_slab_kernel: the ablations are in profiles/r6_slab_findings.md.)
 // K order (chunk, tap, k) and the fp32 epilogue arithmetic are conv_slab_kernel's; measured outputs are bit-identical to it (the 16 x 16 x 32 MFMA evidently
 // folds a K-step's products in the same order as two 32 x 32 x 16 ones); the tests do not rely on that: they state a tolerance.
 #include "tg_gemm_common.h"
@@ -80,14 +80,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     __builtin_amdgcn_sched_barrier(0);                     \
   } while (0)
 
-  // dev timing switches (TG_GEMM_FLAGS, WRONG results by design; scripts/dev_slab_pp.py -> profiles/r6_slab_findings.md): 1 << 16 no weight DMA after the
-  // prologue, 1 << 17 no window staging after the prologue, 1 << 18 no MFMAs
-  // — compiled in only with -DTG_SLAB_DEV_BUILD (the tables of profiles/r6_slab_findings.md came from such a build); constants in the library's build
-#ifdef TG_SLAB_DEV_BUILD
-  const bool ab_now = (p.flags & (1 << 16)) != 0, ab_nos = (p.flags & (1 << 17)) != 0, ab_nom = (p.flags & (1 << 18)) != 0;
-#else
-  constexpr bool ab_now = false, ab_nos = false, ab_nom = false;
-#endif
+  // (where the K-step's time goes — weight DMA, window staging, MFMAs, each switched off in turn in a dev build — is on record in profiles/r6_slab_findings.md)
   if (loader) {
     // =========================================================== loader waves ===========================================
     const int wave = wave12 - 8;
@@ -229,26 +222,25 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap, ++kt) {
           // the next chunk's window: requested at tap 0, landed by the seam of tap 2, normalised in registers in taps 3..8
-          if (tap == 0 && more && !ab_nos) load_slab(cfirst + cc + 1);
-          if (more && !ab_nos) {
+          if (tap == 0 && more) load_slab(cfirst + cc + 1);
+          if (more) {
 #pragma unroll
             for (int j = 0; j < SJ; ++j)
               if ((tap >= 3 && tap <= 5 && j / 2 == tap - 3) || (tap >= 6 && j == tap)) xform_piece(j);
           }
           // seam of K-step kt: weight tile kt + 1 (requested TWO K-steps ago) has landed; tile kt + 2 and, in taps 0 and 1, the window loads may stay in flight
-          if (ab_now || ab_nos) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          else if (kt + 2 < nkt) {
+          if (kt + 2 < nkt) {
             if (tap <= 1 && more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WJ + SJ + NCOEF) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WJ) : "memory");
           } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           if (tap == 2 && more) slab_landed();
           SLAB_BAR();
-          if (kt + 3 < nkt && !ab_now) {            // every compute wave's reads of stage tap % 3 have returned: refill it
+          if (kt + 3 < nkt) {                       // every compute wave's reads of stage tap % 3 have returned: refill it
             const int t3 = tap + 3;
             issue_w(cfirst + (t3 >= 9 ? cc + 1 : cc), t3 >= 9 ? t3 - 9 : t3, tap % 3);
           }
           if (tap == 8 && more) {                   // chunk boundary: the window has been read for the last time
-            if (!ab_nos) write_slab();
+            write_slab();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             SLAB_BAR();                             // X: the next chunk's window is in place
           }
@@ -345,18 +337,16 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         else asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory");
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (!ab_nom) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          // accumulate IN PLACE (tied operand): left to the compiler the 20 accumulator tuples get renamed from MFMA to MFMA (dst != srcC) on a full register
-          // file and the allocator ends up bouncing accumulators or fragment tuples through scratch inside the K loop
-          // (the compiler does not know these statements are MFMAs: it inserts no wait states for an accumulator it reads or moves itself.  The build refuses an
-          // instance whose K loop touches an accumulator outside an MFMA: theatergen_amd/build.py: check_mfma_loops.)
-          if constexpr (sizeof(T) == 2 && std::is_same<T, bf16_t>::value)
-            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc[i][j]) : "v"(j < 4 ? w[j < 4 ? j : 0] : w4c), "v"(xc[i]));
-          else
-            asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc[i][j]) : "v"(j < 4 ? w[j < 4 ? j : 0] : w4c), "v"(xc[i]));
-        }
+      for (int i = 0; i < 4; ++i) {
+        // accumulate IN PLACE (tied operand): left to the compiler the 20 accumulator tuples get renamed from MFMA to MFMA (dst != srcC) on a full register
+        // file and the allocator ends up bouncing accumulators or fragment tuples through scratch inside the K loop
+        // (the compiler does not know these statements are MFMAs: it inserts no wait states for an accumulator it reads or moves itself.  The build refuses an
+        // instance whose K loop touches an accumulator outside an MFMA: theatergen_amd/build.py: check_mfma_loops.)
+        if constexpr (sizeof(T) == 2 && std::is_same<T, bf16_t>::value)
+          asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc[i][j]) : "v"(j < 4 ? w[j < 4 ? j : 0] : w4c), "v"(xc[i]));
+        else
+          asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc[i][j]) : "v"(j < 4 ? w[j < 4 ? j : 0] : w4c), "v"(xc[i]));
       }
       __builtin_amdgcn_sched_barrier(0);
       if (j == 0) {
@@ -600,7 +590,6 @@ int launch_slab_pp(const tg_gemm_desc* d, GemmParams p, int splits, hipStream_t 
   p.tail_s = splits;
   p.kt_per_split = (nchunks + splits - 1) / splits;
   p.tile_bm = BM; p.tile_bn = 320;
-  p.slab_order = ((long)d->N * d->K > (long)d->M * (d->K / 9) && !(p.flags & 8192)) ? 1 : 0;
   long grid = tiles_m * tiles_n * splits;
   if (grid > 256) grid = 256;
   auto k = conv_slab_pp_kernel<T, WI, PRO, PATCH>;

@@ -121,11 +121,11 @@ int launch_gemm(const tg_gemm_desc* d, hipStream_t st) {
   p.tile_bm = pl.bm; p.tile_bn = pl.bn;
   p.a_rpb = d->mode == 0 ? d->a_rows_per_batch : 0; p.a_bs = d->a_batch_stride;
   p.lda = d->lda > 0 ? d->lda : p.c0; p.ldw = d->ldw > 0 ? d->ldw : d->K;
-  p.flags = r.flags;                                  // dev experiments (TG_GEMM_FLAGS); read per launch so one process can A/B
   p.a_coef = d->a_coef; p.a_silu = d->a_silu;
   p.patch_pwl = 0; p.patch_np = 1;
   p.ln_u = d->ln_u; p.ln_v = d->ln_v; p.ln_eps = d->ln_eps; p.ln_rows = d->ln_rows;
   p.epi_lds = r.epi_lds;
+  p.slab_order = r.column_major ? 1 : 0;
   p.gn_part = d->out_gn_partials; p.gn_cpg = d->out_gn_partials ? (int)(d->N / d->out_gn_groups) : 0;
   TG_CHECK(d->out_gn_partials == nullptr || r.gn_partial_blocks > 0, TG_ERR_UNSUPPORTED,
            "tg_gemm: out_gn_partials needs an unsplit stride-1 conv on the two-wave slab kernel with 80 %% (N / groups) == 0 (ask tg_gemm_gn_partial_blocks)");

@@ -248,7 +248,7 @@ void launch_bt_kernel(const GemmParams& p, long grid, size_t lds, hipStream_t st
   // 32 contiguous bytes per token row and instruction (two lanes per row) cost twice the L2 / TA line accesses of the
   // bounce's whole 128-byte rows, for the residual loads as well as for the stores — row-contiguous access wins there.
   if constexpr (EPI == 2) {
-    if (p.epi_lds && p.bvec == nullptr && !(p.flags & 4)) { launch_bt_variant<T, BM, BN, WM, WN, EPI, true>(p, grid, lds, st); return; }
+    if (p.epi_lds && p.bvec == nullptr) { launch_bt_variant<T, BM, BN, WM, WN, EPI, true>(p, grid, lds, st); return; }
   }
   launch_bt_variant<T, BM, BN, WM, WN, EPI, false>(p, grid, lds, st);
 }

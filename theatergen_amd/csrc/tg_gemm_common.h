@@ -45,8 +45,13 @@ struct GemmParams {
   const float* ln_v;    // row statistics from its own A tiles and the epilogue forms rstd * (acc - mean * u[n]) + v[n]; u, v fp32 [N]
   float ln_eps;
   const float* ln_rows; // LN = 2: precomputed (rstd, -rstd * mean) per row, fp32 [M][2] (tg_layernorm_stats)
-  int flags;        // dev experiments (env TG_GEMM_FLAGS): bit 0 = stagger the two co-resident blocks of a CU (low 8 bits = mode,
-                    // bits 8.. = delay in ~1 us units), bit 1 = s_setprio(1) around the MFMA chain
+  // ALWAYS 0: tg_gemm zero-initialises the struct, nothing writes the word and no environment variable reaches it.  A scheduling fence, not a switch.
+  // Three kernel families keep a wave-uniform test of it around s_setprio because hipcc allocates and lays out their K loops differently without the
+  // branch (profiles/gemm_flags_retired_findings.md): gemm_glds_kernel `if (p.sched_fence & 2)` (never taken; without it the bf16 128 x 128 conv
+  // instance goes from 167 to 173 VGPRs and from 3 waves per SIMD to 2, four more instances gain 3 - 5 VGPRs), pp_gemm_kernel / pp160_gemm_kernel
+  // `p.sched_fence == 0` (always taken; without it all ten pp_gemm_kernel instances get other register and spill counts and the MFMA loops of
+  // pp_gemm_kernel<bf16,0,2> and of every pp160_gemm_kernel instance come out in another block order).
+  int sched_fence;
   // slab conv PATCH tiles (tg_conv_slab.hip): a 128-pixel tile = patch_np patches of (128 / patch_np >> patch_pwl) rows x (1 << patch_pwl)
   // columns of an in_h x in_w image, patches numbered image-major / patch-row / patch-column.  patch_pwl = 0: tile rows are contiguous tokens.
   int patch_pwl, patch_np;
@@ -54,7 +59,8 @@ struct GemmParams {
   const void* xa_kv;          // [batch][N / 160 tiles][pieces of 1 KiB]: K / V^T MFMA fragments of the tile's heads (tg_xq_kv_pack)
   const float* xa_ip_scale;   // device scalar (IPAttnProcessor.scale) or NULL (1.0)
   int xa_rows_per_batch, xa_tiles_n, xa_L, xa_T;
-  int slab_order;   // slab conv work order: 0 tile-major, 1 (column tile, split)-major / row-tile-minor (weight-heavy layers)
+  int slab_order;   // work order of the persistent kernels (GemmRoute::column_major): 0 tile-major; 1 slab conv (column tile, split)-major / row-tile-minor,
+                    // ping-pong tiles column-major
   float* gn_part;   // two-wave slab conv, unsplit: GroupNorm partial sums of the output, fp32 [batch][hw / 64][N / gn_cpg][2] (tg_gemm_desc.out_gn_partials), or NULL
   int gn_cpg;       // ... channels per group (divides 80)
 };
@@ -110,30 +116,6 @@ __device__ __forceinline__ void epilogue_store4(const GemmParams& p, long m, lon
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = from_f32<T>(v[j]);
     *reinterpret_cast<V4*>(reinterpret_cast<T*>(p.out) + m * p.ldc + n4) = o;
-  }
-}
-
-// EXPERIMENT (TG_GEMM_FLAGS bit 0): the two blocks that share a CU start together and have identical work, so they sit in
-// their K loops together (each with half the matrix pipe) and in their epilogues together (matrix pipe idle).  Delay ONE of
-// the two first-round blocks of every CU by about half a tile period so that one block's epilogue overlaps the other's K
-// loop; later rounds inherit the offset (a finished block is replaced at once).  CU identity from the hardware id registers,
-// arrival parity from a never-reset global counter (consecutive arrivals on one CU differ in parity).  Speed only.
-__device__ unsigned int tg_cu_arrivals[2048];
-__device__ __forceinline__ void stagger_first_round(int flags, char* smem_base) {
-  if (!(flags & 1) || gridDim.x < 512 || blockIdx.x >= 512) return;
-  int* dec = reinterpret_cast<int*>(smem_base);
-  if (threadIdx.x == 0) {
-    const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);        // HW_REG_HW_ID: cu_id [11:8], sh_id [12], se_id [15:13]
-    const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);      // HW_REG_XCC_ID
-    const unsigned key = ((xcc & 7u) << 8) | ((hw >> 8) & 0xffu);
-    *dec = (int)(atomicAdd(&tg_cu_arrivals[key], 1u) & 1u);
-  }
-  __syncthreads();
-  const int late = *dec;
-  __syncthreads();
-  if (late) {
-    const int units = (flags >> 8) & 0xff;
-    for (int i = 0; i < units; ++i) __builtin_amdgcn_s_sleep(32);         // ~2048 cycles ~ 1 us each
   }
 }
 

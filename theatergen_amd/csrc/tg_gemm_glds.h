@@ -73,7 +73,6 @@ void gemm_glds_kernel(GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* sX = reinterpret_cast<T*>(smem);                 // [2][BM][64]
   T* sW = sX + STAGES * BM * BKT;                     // [STAGES][BN][BKT]
-  stagger_first_round(p.flags, smem);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -312,7 +311,7 @@ void gemm_glds_kernel(GemmParams p) {
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (p.flags & 2) __builtin_amdgcn_s_setprio(1);
+      if (p.sched_fence & 2) __builtin_amdgcn_s_setprio(1);      // never taken: a scheduling fence (GemmParams::sched_fence)
 #pragma unroll
       for (int ks = 0; ks < BKT / 16; ++ks) {
         if constexpr (BIGW) {
@@ -337,7 +336,7 @@ void gemm_glds_kernel(GemmParams p) {
 #pragma unroll
           for (int j = 0; j < TN; ++j) acc[i][j] = mfma32(wf[ks][j], xf[ks][i], acc[i][j]);
       }
-      if (p.flags & 2) __builtin_amdgcn_s_setprio(0);
+      if (p.sched_fence & 2) __builtin_amdgcn_s_setprio(0);
       if constexpr (LN == 1) {
         if constexpr (!ER) {
           __builtin_amdgcn_sched_barrier(0);

@@ -113,8 +113,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #undef PP_READ
   f32x4 acc[2][2][4][2];                          // [qa][qb][i][j]: tokens qa * 64 + i * 16 + frow, channels qb * 32 + j * 16 + 4 fq + e
   // s_setprio 1 around a phase's MFMA block (guide T5: the phase split gives the arbiter something to prefer): same-box A/B 842.8 -> 839.9 ms per story
-  // (profiles/r6_ab_prio.json); TG_GEMM_FLAGS bit 15 (dev) switches it off
-  const bool prio = (p.flags & 32768) == 0;
+  // (profiles/r6_ab_prio.json).  Always on: GemmParams::sched_fence is 0.  The test stays because hipcc schedules the K loop differently around an
+  // unconditional s_setprio (see the field's comment for the numbers)
+  const bool prio = p.sched_fence == 0;
   auto mfma_quad = [&](int qa, int qb) {
     if (prio) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -395,9 +396,6 @@ int launch_pp(const GemmParams& p0, hipStream_t st) {
   const long tiles_m = p.M / 256, tiles_n = p.N / 256;
   p.tiles_n = (int)tiles_n;
   p.tile_bm = 256; p.tile_bn = 256; p.full_tiles = (int)(tiles_m * tiles_n); p.tail_s = 1;
-  // tile walk: column-major when the weight is the larger operand (an XCD's chunk then covers whole weight column panels: FeedForward net.0 of the
-  // 16 x 16 level, 4096 x 10240 x 1280, moved 578 MB per launch against 79 MB algorithmic on row-major 128 x 128 tiles, profiles/r5_pmc_traffic.json)
-  p.slab_order = ((long)p.N > p.M && !(p.flags & 8192)) ? 1 : 0;
   long grid = tiles_m * tiles_n;
   if (grid > 256) grid = 256;
   auto k = pp_gemm_kernel<T, EPI, LN>;

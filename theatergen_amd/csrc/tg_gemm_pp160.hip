@@ -94,7 +94,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     P160_READ(xf[0], a, 0); P160_READ(xf[1], a, 2048); P160_READ(xf[2], a, 4096); P160_READ(xf[3], a, 6144);
   };
 #undef P160_READ
-  const bool prio = (p.flags & 32768) == 0;       // s_setprio 1 around a phase's MFMA block (tg_gemm_pp.hip); TG_GEMM_FLAGS bit 15 (dev) switches it off
+  const bool prio = p.sched_fence == 0;           // s_setprio 1 around a phase's MFMA block, always on (tg_gemm_pp.hip; GemmParams::sched_fence)
   auto mfmas = [&]() {
     if (prio) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -281,7 +281,6 @@ int launch_pp160(const GemmParams& p0, hipStream_t st) {
   const long tiles_m = p.M / 256, tiles_n = p.N / 160;
   p.tiles_n = (int)tiles_n;
   p.tile_bm = 256; p.tile_bn = 160; p.full_tiles = (int)(tiles_m * tiles_n); p.tail_s = 1;
-  p.slab_order = ((long)p.N > p.M && !(p.flags & 8192)) ? 1 : 0;
   auto k = pp160_gemm_kernel<T, EPI, LN>;
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   (void)attr;

@@ -31,7 +31,8 @@ enum GemmForceTile {
 
 // The dev A/B knobs of the planner.  Read once per route, never cached: tests and A/B scripts change them inside one process.
 struct GemmKnobs {
-  long flags;     // TG_GEMM_FLAGS (default 0): bit 3 no big tile, 7 no slab kernel, 10 no patch tiles, 11 / 12 the slab split rules; kernels read the rest (GemmParams::flags)
+  long flags;     // TG_GEMM_FLAGS (default 0), the router's five bits and nothing else: bit 3 no big tile, 7 no slab kernel, 10 no patch tiles, 11 / 12 the slab split
+                  // rules.  Every other bit of the variable is masked off (kGemmRouterFlags): no kernel and no launcher sees the word
   int pp;         // TG_PP (15): 1 = GEGLU, 2 = linear / activation, 4 = LayerNorm-folded launches on the ping-pong tiles, 8 = the 256 x 160 tiles
   int t160;       // TG_T160 (7): 1 = 128 x 160 tiles for plain GEMMs where they fill whole rounds, 2 = for the LayerNorm-folded projections, 4 = N = 2.5 / 7.5 tiles of 128
   long t64_max;   // TG_T64_MAX (128): 128 x 128 tile counts up to this take the 64 x 64 tile
@@ -58,7 +59,7 @@ struct GemmRoute {
   int gn_partial_blocks;        // > 0: the kernel can write GroupNorm partial sums of its output: 64-pixel blocks per batch item
   const char* kernel;           // the kernel template's name
   bool epi_lds;                 // operands / strides allow the LDS-transposed, 16-byte-coalesced epilogue (GemmParams::epi_lds)
-  int flags;                    // GemmParams::flags
+  bool column_major;            // kKindSlab / kKindPingPong: the persistent grid walks column tiles outermost (GemmParams::slab_order): the weight is the larger operand
   // tg_gemm refuses the descriptor with this code / message (TG_OK: it launches).  The queries answer for such a descriptor as they always have.
   int refusal;
   const char* refusal_msg;

@@ -27,6 +27,9 @@ constexpr int kNumTiles = 10;
 // (8192x4096x4096 929 vs 839 TF, 16384x5120x2560 1001 vs 818) but no gain at the SD-1.5 UNet's K = 320..1280 with the GEGLU
 // epilogue (scripts/dev_big_tile.py), so it is forced-only for now
 
+// TG_GEMM_FLAGS bits the planner reads (slab_splits_of, big_tile_selected); what else the variable holds reaches nothing
+constexpr long kGemmRouterFlags = 8 | 128 | 1024 | 2048 | 4096;
+
 long env_long(const char* name, long dflt) {
   const char* e = getenv(name);
   return e ? strtol(e, nullptr, 0) : dflt;
@@ -326,7 +329,7 @@ int refuse(GemmRoute* r, int code, const char* msg) {
 
 GemmKnobs gemm_knobs() {
   GemmKnobs k;
-  k.flags = env_long("TG_GEMM_FLAGS", 0);
+  k.flags = env_long("TG_GEMM_FLAGS", 0) & kGemmRouterFlags;
   k.pp = (int)env_long("TG_PP", 15);
   k.t160 = (int)env_long("TG_T160", 7);
   k.t64_max = env_long("TG_T64_MAX", 128);
@@ -341,7 +344,6 @@ GemmKnobs gemm_knobs() {
 int gemm_route(const tg_gemm_desc* d, GemmRoute* r) {
   const GemmKnobs kn = gemm_knobs();
   *r = GemmRoute{};
-  r->flags = (int)kn.flags;
   r->epi_lds = epi_lds_of(d);
   r->plan = make_plan(d, kn);
   r->slab_np = 1;
@@ -350,6 +352,9 @@ int gemm_route(const tg_gemm_desc* d, GemmRoute* r) {
   r->pp_bn = pp_selected(d, kn, 256) ? 256 : (pp_selected(d, kn, 160) ? 160 : 0);
   if (r->pp_bn != 0) {
     set_family(r, kKindPingPong, r->pp_bn == 256 ? "pp_gemm_kernel" : "pp160_gemm_kernel", 256, r->pp_bn, 1);
+    // tile walk: column-major when the weight is the larger operand (an XCD's chunk then covers whole weight column panels: FeedForward net.0 of the
+    // 16 x 16 level, 4096 x 10240 x 1280, moved 578 MB per launch against 79 MB algorithmic on row-major 128 x 128 tiles, profiles/r5_pmc_traffic.json)
+    r->column_major = d->N > d->M;
     return TG_OK;
   }
   // a forced ping-pong tile on a problem it cannot take: the queries go on down the chain, tg_gemm refuses
@@ -367,6 +372,8 @@ int gemm_route(const tg_gemm_desc* d, GemmRoute* r) {
     set_family(r, kKindSlab, r->two_wave ? "conv_slab_pp_kernel" : "conv_slab_kernel", 128, 320, sp);
     r->workspace_bytes = sp > 1 ? (d->M / 128) * (d->N / 320) * sp * 128 * 320 * 4 : 0;
     r->gn_partial_blocks = slab_gn_partial_blocks(d, *r);
+    // weight-heavy layer (more weight than activation elements): (column tile, split)-major work order (tg_conv_slab.hip: work_item)
+    r->column_major = d->N * d->K > d->M * (d->K / 9);
     return r->refusal;
   }
   r->slab_pw = 0; r->slab_np = 1; r->slab_patch = false;

@@ -497,8 +497,10 @@ int tg_scale_repeat(int32_t dtype, const void* x, int64_t n, float scale, int32_
  * tg_sumpool2x2     : sum over the 2 x 2 block of an upsampled token-major map [batch, 2h, 2w, C] -> [batch, h, w, C] (Upsample2D)
  */
 /* `partials`: fp32 scratch of tg_groupnorm_bwd_scratch_bytes(batch, hw, groups) — the rows of a batch item are cut into slabs so that the
- * batch-1 backward pass spreads over the chip (three launches: statistics, gradient sums, apply; fixed-order folds).  NULL, or channels not a
- * multiple of 8, runs the one-workgroup-per-(item, group) kernel. */
+ * batch-1 backward pass spreads over the chip (three launches: statistics, gradient sums, apply; fixed-order folds).  The slab kernels form the
+ * variance in one pass (E[x^2] - mean^2 from fp32 slab sums folded in fp64).  Any of five conditions runs the one-workgroup-per-(item, group)
+ * kernel instead, which centres first and touches neither `partials` nor 16-byte accesses: `partials` NULL; channels not a multiple of 8;
+ * channels > 4096; groups > 256; x, dy, dx, gamma or beta not 16-byte aligned. */
 int64_t tg_groupnorm_bwd_scratch_bytes(int32_t batch, int64_t hw, int32_t groups);
 int tg_groupnorm_bwd(int32_t dtype, const void* x, const void* dy, int32_t batch, int64_t hw, int32_t channels, int32_t groups, float eps,
                      const void* gamma, const void* beta, int32_t silu, void* dx, void* partials, void* stream);

@@ -324,7 +324,11 @@ int tg_attention_bwd_cross_wide(const tg_attn_bwd_cross_desc* d, void* stream);
 
 /* Attention-probability export (the save_attn_to_dict side channel, attention_processor.py:532-551):
  * probs[b - b0, h, i, t] = softmax_j(s q_i . k_j)[tokens[t]] for batch items b in [b0, batch), fp32 out
- * [batch - b0, heads, n_q, n_tokens].  tokens == NULL: all `len` columns.  */
+ * [batch - b0, heads, n_q, n_tokens].  tokens == NULL: all `len` columns (n_tokens is ignored), else tokens[t] in [0, len) and n_tokens > 0.
+ * q row i of item b starts at q + b * q_bs + i * q_ld (+ head * head_dim), k row j at k + b * k_bs + j * k_ld; rows of items below b0 are not read.
+ * One wave per query row (attn_probs_kernel).  TG_ERR_ARG, before any launch: len outside 1..256, head_dim <= 0 or no multiple of 8, q_ld or k_ld no
+ * multiple of 8 (the kernel reads 16 bytes at a time; q, k and the batch strides must keep that alignment too), tokens != NULL with n_tokens <= 0,
+ * batch <= b0, b0 < 0, heads or n_q <= 0, NULL q / k / probs. */
 int tg_attn_probs(int32_t dtype, int32_t batch, int32_t b0, int32_t heads, int32_t head_dim, int32_t n_q,
                   const void* q, int64_t q_ld, int64_t q_bs, const void* k, int64_t k_ld, int64_t k_bs,
                   int32_t len, float scale, const int32_t* tokens, int32_t n_tokens, float* probs, void* stream);
@@ -363,7 +367,7 @@ int tg_groupnorm_from_partials(int32_t dtype, const void* x, int32_t C, int32_t 
 
 /* out[m, j] = x[m, j] * gelu(x[m, inner + j])  (GEGLU.forward, models/attention.py:337-338) */
 int tg_geglu(int32_t dtype, const void* x, int64_t rows, int64_t inner, void* out, void* stream);
-/* out = act(x) elementwise (n elements) */
+/* out = act(x) elementwise (n elements): act 0 identity, 1 SiLU, 2 GELU (erf), 3 quick GELU x sigmoid(1.702 x); any other code is the identity */
 int tg_act(int32_t dtype, const void* x, int64_t n, int32_t act, void* out, void* stream);
 /* out = a + b (n elements; ControlNet residual injection, models/unet_2d_condition.py:938-946, 975-976) */
 int tg_add(int32_t dtype, const void* a, const void* b, int64_t n, void* out, void* stream);
@@ -373,7 +377,9 @@ int tg_add(int32_t dtype, const void* a, const void* b, int64_t n, void* out, vo
 int tg_dup_rows(const void* src, void* dst, int64_t rows, int64_t cols, int64_t ld, int32_t dtype, void* stream);
 
 /* dst[b, c, r] = src[b, r, c]: NCHW <-> token-major conversion for the processors' 4-D input path
- * (attention_processor.py:318-320, 363-364) and ControlNet residual injection (models/unet_2d_condition.py:938-946). */
+ * (attention_processor.py:318-320, 363-364) and ControlNet residual injection (models/unet_2d_condition.py:938-946).
+ * Kernel gates: rows % 128 == 0, cols % 64 == 0 and src, dst 16-byte aligned -> transpose_big_kernel (128 x 64 tiles, 16-byte accesses);
+ * everything else -> transpose_kernel (32 x 32 tiles, ragged edges masked).  src == dst is TG_ERR_ARG. */
 int tg_transpose(int32_t dtype, const void* src, int32_t batch, int32_t rows, int32_t cols, void* dst, void* stream);
 
 /* VAE decode helpers (AutoencoderKL.decode as called at models/pipelines.py:468, 849-854; diffusers 0.21.4):
@@ -391,7 +397,19 @@ int tg_softmax_rows(int32_t dtype, const void* x, int64_t rows, int32_t cols, in
  * tg_conv_in : sample NCHW [batch, cin, h, w] (src_dtype: 0 bf16, 1 f16, 2 f32) -> NHWC [batch, h*w, cout],
  *              3x3 pad 1, weight [cout, 3, 3, cin] + bias  (conv_in, models/unet_2d_condition.py:294-297, 879)
  * tg_conv_out: NHWC [batch, h*w, cin] (already GroupNorm+SiLU'ed) -> NCHW fp32|dtype [batch, cout, h, w]
- *              (conv_out, models/unet_2d_condition.py:583-586, 1018)
+ *              (conv_out, models/unet_2d_condition.py:583-586, 1018); weight [cout, 3, 3, cin]; bias may be NULL in both
+ * Argument checks (TG_ERR_ARG, before any launch):
+ *   tg_conv_in / tg_conv_in_dup : batch, h, w, cout > 0, 0 < cin <= 16, src_dtype in 0..2, non-NULL sample / weight / out
+ *   tg_conv_out / tg_conv_out_gn: batch, h, w > 0, cin > 0 and cin % 8 == 0, 0 < cout <= 8, non-NULL x / weight / out; tg_conv_out_gn: non-NULL coef
+ * Kernel gates, first match wins (the result is the same convolution on every kernel, to rounding):
+ *   tg_conv_in : conv_in_mfma_kernel  cin == 4, cout % 160 == 0, cout <= 640, out 16-byte and weight 8-byte aligned
+ *                conv_in_fast_kernel  cout % 8 == 0, cout / 8 <= 256, out 16-byte aligned, and with G = cout / 8, groups = 256 / G:
+ *                                     (9 cin cout + 2 groups 9 cin) * 4 bytes of LDS <= 65536
+ *                conv_in_kernel       the rest
+ *   tg_conv_out: conv_out_mfma_kernel cin % 64 == 0, cin <= 320, cout <= 8, h % 8 == 0, w % 16 == 0, x and weight 16-byte aligned;
+ *                                     LDS (180 cin + 9 cin cout) * 2 + 8 cin bytes: 163840, the whole 160 KiB, at cin = 320, cout = 8
+ *                conv_out_fast_kernel<4> (cout <= 4) / <8>: 9 cin cout * 2 bytes of LDS <= 65536, x and weight 16-byte aligned
+ *                conv_out_kernel      the rest
  */
 int tg_conv_in(int32_t dtype, const void* sample, int32_t src_dtype, int32_t batch, int32_t cin, int32_t h, int32_t w,
                const void* weight, const void* bias, int32_t cout, void* out, void* stream);

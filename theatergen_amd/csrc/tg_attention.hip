@@ -540,7 +540,11 @@ extern "C" int tg_attn_probs(int32_t dtype, int32_t batch, int32_t b0, int32_t h
                              int32_t len, float scale, const int32_t* tokens, int32_t n_tokens, float* probs, void* stream) {
   TG_CHECK(dtype == TG_BF16 || dtype == TG_F16, TG_ERR_ARG, "tg_attn_probs: bad dtype");
   TG_CHECK(q && k && probs && batch > b0 && b0 >= 0 && heads > 0 && n_q > 0, TG_ERR_ARG, "tg_attn_probs: bad args");
-  TG_CHECK(len > 0 && len <= 256 && head_dim % 8 == 0, TG_ERR_ARG, "tg_attn_probs: len (%d) must be in 1..256", len);
+  TG_CHECK(len > 0 && len <= 256 && head_dim > 0 && head_dim % 8 == 0, TG_ERR_ARG, "tg_attn_probs: len (%d) must be in 1..256, head_dim (%d) a positive multiple of 8", len,
+           head_dim);
+  TG_CHECK(q_ld % 8 == 0 && k_ld % 8 == 0, TG_ERR_ARG, "tg_attn_probs: q_ld (%lld) and k_ld (%lld) must keep the 16-byte loads aligned (multiples of 8)", (long long)q_ld,
+           (long long)k_ld);
+  TG_CHECK(tokens == nullptr || n_tokens > 0, TG_ERR_ARG, "tg_attn_probs: n_tokens (%d) must be positive when tokens is given", n_tokens);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   dim3 grid((unsigned)((n_q + 3) / 4), (unsigned)heads, (unsigned)(batch - b0));
   if (dtype == TG_BF16)

@@ -751,7 +751,7 @@ extern "C" int tg_conv_in(int32_t dtype, const void* sample, int32_t src_dtype, 
 extern "C" int tg_conv_in_dup(int32_t dtype, const void* sample, int32_t src_dtype, int32_t batch, int32_t cin, int32_t h,
                               int32_t w, const void* weight, const void* bias, int32_t cout, void* out, int64_t dup_offset, void* stream) {
   TG_CHECK((dtype == TG_BF16 || dtype == TG_F16) && sample && weight && out, TG_ERR_ARG, "tg_conv_in: bad args");
-  TG_CHECK(src_dtype >= 0 && src_dtype <= 2 && batch > 0 && cin > 0 && cin <= 16 && cout > 0, TG_ERR_ARG, "tg_conv_in: bad shape");
+  TG_CHECK(src_dtype >= 0 && src_dtype <= 2 && batch > 0 && cin > 0 && cin <= 16 && cout > 0 && h > 0 && w > 0, TG_ERR_ARG, "tg_conv_in: bad shape");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const long npix = (long)batch * h * w;
   {
@@ -819,7 +819,8 @@ extern "C" int tg_conv_out_takes_coef(int32_t cin, int32_t h, int32_t w, int32_t
 static int conv_out_impl(int32_t dtype, const void* x, const float* coef, int32_t a_silu, int32_t batch, int32_t cin, int32_t h, int32_t w,
                          const void* weight, const void* bias, int32_t cout, void* out, int32_t out_f32, void* stream) {
   TG_CHECK((dtype == TG_BF16 || dtype == TG_F16) && x && weight && out, TG_ERR_ARG, "tg_conv_out: bad args");
-  TG_CHECK(batch > 0 && cin % 8 == 0 && cout > 0 && cout <= 8, TG_ERR_ARG, "tg_conv_out: bad shape cin=%d cout=%d", cin, cout);
+  TG_CHECK(batch > 0 && cin > 0 && cin % 8 == 0 && cout > 0 && cout <= 8 && h > 0 && w > 0, TG_ERR_ARG, "tg_conv_out: bad shape cin=%d cout=%d h=%d w=%d", cin, cout,
+           h, w);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const long npix = (long)batch * h * w;
   if (conv_out_mfma_ok(cin, h, w, cout) && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(weight) & 15) == 0) {

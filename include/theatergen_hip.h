@@ -228,6 +228,15 @@ typedef struct {
 } tg_attn_desc;
 
 int tg_attention(const tg_attn_desc* d, void* stream);
+/* Per-batch-item weight of segment 1 (the IP-Adapter scale of each image of a batched denoising step; the reference sets it per character,
+ * models/pipelines.py:183-199: 0.4 with a database image, 0 for a first appearance).  The descriptor is tg_attention's, unchanged; `ip_scale_count` says
+ * how many floats `w1_dev` points at:
+ *     0 or 1     one float, as tg_attention reads it (tg_attention IS this call with 0);
+ *     d->batch   one float per batch item: block (b, head, query block) forms  f = w1_dev[b] / l1  where the scalar call forms  w1_dev[0] / l1 —
+ *                the same instruction on another address, so item b's rows are bit-equal to a scalar launch with w1_dev[b].
+ * TG_ERR_ARG before any launch: any other count; a count > 1 with w1_dev == NULL.  Every other check is tg_attention's.
+ * Additive to ABI 308: one new symbol, tg_attn_desc unchanged, TG_ABI_VERSION unchanged. */
+int tg_attention_ps(const tg_attn_desc* d, int32_t ip_scale_count, void* stream);
 /* The same descriptor for WIDE heads, head_dim 256 or 512, ONE softmax segment (csrc/tg_attention_wide.hip; the VAE mid block's single-head d = C attention):
  *     O = softmax(s Q K0^T) V0
  * Nothing [n_q, len0] exists in memory: scores are accumulated in fp32 from the stored q / k0, the softmax is online (running max and sum in fp32), P is
@@ -655,6 +664,11 @@ typedef struct {
   const float* ip_scale;
 } tg_rc_xattn_desc;
 int tg_rc_xattn(const tg_rc_xattn_desc* d, void* stream);
+/* tg_rc_xattn with `ip_scale` as ONE FLOAT PER BATCH ITEM: ip_scale_count 0 or 1 = one float (tg_rc_xattn is this call with 0); M / rows_per_batch = the
+ * workgroup of batch item b weights the image keys with ip_scale[b] (a workgroup's 128 tokens lie inside one item: the rows_per_batch check above).  Any
+ * other count, or a count > 1 with ip_scale == NULL, is TG_ERR_ARG before any launch.
+ * Additive to ABI 308: one new symbol, tg_rc_xattn_desc unchanged, TG_ABI_VERSION unchanged. */
+int tg_rc_xattn_ps(const tg_rc_xattn_desc* d, int32_t ip_scale_count, void* stream);
 int tg_rc_kv_pack(int32_t dtype, int32_t batch, const void* k, const void* vt, int64_t ldt, int32_t text_len, const void* kip,
                   const void* vtip, int64_t ldi, int32_t ip_tokens, void* out, void* stream);
 
@@ -764,6 +778,11 @@ typedef struct {
   int32_t C, head_dim, rows_per_batch, text_len, ip_tokens;
 } tg_xq_attn_desc;
 int tg_xq_attn(const tg_xq_attn_desc* d, void* stream);
+/* tg_xq_attn with `ip_scale` as ONE FLOAT PER BATCH ITEM, every head dim (64, 80, 160): ip_scale_count 0 or 1 = one float (tg_xq_attn is this call with 0);
+ * M / rows_per_batch = the 128-token tile of batch item b (m0 / rows_per_batch) weights the image keys with ip_scale[b] before the probabilities are
+ * rounded, as the scalar does.  Any other count, or a count > 1 with ip_scale == NULL, is TG_ERR_ARG before any launch.
+ * Additive to ABI 308: one new symbol, tg_xq_attn_desc unchanged, TG_ABI_VERSION unchanged. */
+int tg_xq_attn_ps(const tg_xq_attn_desc* d, int32_t ip_scale_count, void* stream);
 int64_t tg_xq_kv_bytes(int32_t batch, int32_t C, int32_t head_dim);
 int tg_xq_kv_pack(int32_t dtype, int32_t batch, int32_t C, int32_t head_dim, const void* k, const void* vt, int64_t ldt, int32_t text_len, const void* kip,
                   const void* vtip, int64_t ldi, int32_t ip_tokens, void* out, void* stream);

@@ -138,6 +138,7 @@ SIGNATURES = {
     "tg_gemm_plan": (i32, [C.POINTER(GemmDesc), vp, vp, vp, vp]),
     "tg_gemm_kernel_name": (C.c_char_p, [C.POINTER(GemmDesc)]),
     "tg_attention": (i32, [C.POINTER(AttnDesc), vp]),
+    "tg_attention_ps": (i32, [C.POINTER(AttnDesc), i32, vp]),
     "tg_attention_wide": (i32, [C.POINTER(AttnDesc), vp]),
     "tg_attention_wide_splits": (i32, [C.POINTER(AttnDesc), i32]),
     "tg_attention_wide_workspace_bytes": (i64, [C.POINTER(AttnDesc), i32]),
@@ -196,11 +197,13 @@ SIGNATURES = {
     "tg_rc_linear": (i32, [C.POINTER(RcLinearDesc), vp]),
     "tg_rc_linear_dup": (i32, [C.POINTER(RcLinearDesc), i64, vp]),
     "tg_rc_xattn": (i32, [C.POINTER(RcXattnDesc), vp]),
+    "tg_rc_xattn_ps": (i32, [C.POINTER(RcXattnDesc), i32, vp]),
     "tg_rc_kv_pack": (i32, [i32, i32, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp]),
     "tg_rc_ff": (i32, [C.POINTER(RcFfDesc), vp]),
     "tg_rc_front": (i32, [C.POINTER(RcFrontDesc), vp]),
     "tg_skinny_gemm": (i32, [C.POINTER(SkinnyDesc), vp]),
     "tg_xq_attn": (i32, [C.POINTER(XqAttnDesc), vp]),
+    "tg_xq_attn_ps": (i32, [C.POINTER(XqAttnDesc), i32, vp]),
     "tg_xq_kv_bytes": (i64, [i32, i32, i32]),
     "tg_xq_kv_pack": (i32, [i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp]),
     "tg_debug_mfma32": (i32, [i32, vp, vp, vp, vp]),

@@ -74,19 +74,59 @@ def _live_replay_streams(device):
     return [st for d, st in _REPLAY_STREAMS if d == device]
 
 
-def fenced_fill(t, value):
-    """``t.fill_(value)`` on the current stream, ordered after everything queued on the registered replay streams and before whatever they run next"""
+def _fenced(t, write):
+    """``write()`` (a write of ``t`` queued on the current stream), ordered after everything queued on the registered replay streams and before whatever
+    they run next"""
     dev = t.device
     if dev.type != "cuda" or torch.cuda.is_current_stream_capturing():
-        t.fill_(value)
+        write()
         return
     cur = torch.cuda.current_stream(dev)
     others = [st for st in _live_replay_streams(dev) if st != cur]
     for st in others:
         cur.wait_stream(st)
-    t.fill_(value)
+    write()
     for st in others:
         st.wait_stream(cur)
+
+
+def fenced_fill(t, value):
+    """``t.fill_(value)`` on the current stream, ordered after everything queued on the registered replay streams and before whatever they run next"""
+    _fenced(t, lambda: t.fill_(value))
+
+
+def fenced_copy(t, values):
+    """``t.copy_(values)`` (a host sequence of ``t.numel()`` floats) with the ordering of ``fenced_fill``.  Not inside a stream capture: the source is
+    pageable host memory, and a copy from it cannot be recorded into a graph (the number form's ``fill_`` can)."""
+    if t.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("IPAttnProcessor.scale: per-batch-item values cannot be assigned while a stream capture is running (the host-to-device copy "
+                           "cannot be recorded); assign them before the capture, or assign a number")
+    src = torch.tensor([float(v) for v in values], dtype=t.dtype)
+    _fenced(t, lambda: t.copy_(src))
+
+
+def scale_vector(value):
+    """None for a plain number (and for a 0-d tensor: the reference's scalar); else the 1-D sequence / tensor ``value`` as a tuple of floats"""
+    if getattr(value, "ndim", 1) == 0:
+        return None
+    if torch.is_tensor(value):
+        if value.ndim != 1:
+            raise ValueError(f"IPAttnProcessor.scale: a per-batch-item scale is 1-D, got shape {tuple(value.shape)}")
+        return tuple(float(v) for v in value.detach().cpu().tolist())
+    if isinstance(value, (list, tuple)) or (hasattr(value, "__len__") and hasattr(value, "__iter__") and not isinstance(value, (str, bytes))):
+        vals = list(value)
+        if not vals or any(hasattr(v, "__len__") and not torch.is_tensor(v) for v in vals):
+            raise ValueError("IPAttnProcessor.scale: a per-batch-item scale is a non-empty 1-D sequence of numbers")
+        return tuple(float(v) for v in vals)
+    return None
+
+
+def host_ip_scale(proc, what):
+    """``float(proc.scale)`` for the paths that take the IP scale as a host constant; a per-batch-item scale is refused, never cut to its first element"""
+    if isinstance(proc.scale, tuple):
+        raise NotImplementedError(f"theatergen_amd: {what} takes the IP-Adapter scale as one host constant; IPAttnProcessor.scale holds "
+                                  f"{len(proc.scale)} per-batch-item values (assign a number, or run the items one at a time)")
+    return float(proc.scale)
 
 
 class StaticSlots:
@@ -480,7 +520,7 @@ def fused_cross_block(attn, norm, x2d, B, N, enc, kwargs):
     if is_ip:
         enc_c = enc.contiguous()
         kvpk = proc.project_kv_frags(attn, enc_c)
-        scale_dev = proc.scale_device(x2d.device)
+        scale_dev = proc.scale_device(x2d.device, B)
     else:
         e, Lr, enc_bs = _enc_rows(enc)
         ldt = _round8(L)
@@ -579,7 +619,7 @@ class IPAttnProcessor(nn.Module):
         super().__init__()
         self.hidden_size = hidden_size
         self.cross_attention_dim = cross_attention_dim
-        self._scale_dev = None          # fp32 [1] on the compute device: what the kernel reads (see the ``scale`` property)
+        self._scale_bufs = {}           # {(device, n): fp32 [n]}: what the kernels read; made on first use, never freed (see the ``scale`` property)
         self.scale = scale
         self.num_tokens = num_tokens
         self.to_k_ip = nn.Linear(cross_attention_dim or hidden_size, hidden_size, bias=False)
@@ -591,24 +631,72 @@ class IPAttnProcessor(nn.Module):
     # ip_adapter/ip_adapter.py:155-158; ``custom_pipelines.py:328-333`` toggles 0.0 <-> s per step), but the value the attention
     # kernel multiplies with lives in a DEVICE scalar: an assignment refreshes that scalar (one 4-byte fill on the current
     # stream), so a hipGraph captured with one scale replays with the next one — no re-capture, no host sync.
-    # STREAM CONTRACT (round 5): the fill is issued on the current stream AND fenced against every registered replay stream (``fenced_fill``:
-    # the engine-owned streams of ``DenoiseEngine.run_concurrent`` register themselves), so an assignment between two replays — on whichever stream
-    # they run — is seen by the second and never lands under the first.  Engines that share one UNet share this scalar (one IP scale per UNet at a
-    # time); assigning it from ANOTHER THREAD while a loop runs is still unordered on the host side.
+    # STREAM CONTRACT (round 5): the write is issued on the current stream AND fenced against every registered replay stream (``fenced_fill`` /
+    # ``fenced_copy``: the engine-owned streams of ``DenoiseEngine.run_concurrent`` register themselves), so an assignment between two replays — on
+    # whichever stream they run — is seen by the second and never lands under the first.  Engines that share one UNet share these values (one IP
+    # scale, or one vector of them, per UNet at a time); assigning from ANOTHER THREAD while a loop runs is still unordered on the host side.
+    # PER-BATCH-ITEM FORM: a 1-D sequence / tensor assigns one value per batch item of the calls that follow (``DenoiseEngine.set_ip_scale``: the reference
+    # generates a known character at 0.4 and a first appearance at 0, models/pipelines.py:183-199 — a batched step mixes them) and reads back as a tuple of
+    # floats; the kernels then read element ``b`` for batch item ``b`` (tg_*_ps).
+    # BUFFERS ARE NEVER FREED OR MOVED: one fp32 buffer per (device, length) — [1] and one [n] per vector length ever used —, made on first use and kept
+    # for the processor's lifetime, because a captured graph (``DenoiseEngine``, ``backward.GraphedInputGrad``, a caller's own) holds the address of the
+    # one it was captured with.  EVERY assignment writes ALL of them: a number fills each buffer (so a step captured in the per-item form replays
+    # correctly under the per-step gating, which assigns plain numbers); a vector is copied into the buffer of its length and every other buffer is
+    # filled with NaN — a graph captured with another count has no right answer to replay, and its owner is expected to look first
+    # (``DenoiseEngine._signature`` / ``GraphedInputGrad.run`` compare ``scale_count``); if one does not, its output is NaN, not a plausible image.
+    # Once a [n] buffer exists, calls of batch n read it in either form (``scale_count`` is sticky), so going back to a number re-captures nothing.
     @property
     def scale(self):
         return self._scale
 
     @scale.setter
     def scale(self, value):
-        self._scale = value
-        if self._scale_dev is not None:
-            fenced_fill(self._scale_dev, float(value))
+        vec = scale_vector(value)
+        if vec is None:
+            self._scale = value
+            for buf in self._scale_bufs.values():
+                fenced_fill(buf, float(value))
+            return
+        if any(dev.type == "cuda" for dev, _ in self._scale_bufs) and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("IPAttnProcessor.scale: per-batch-item values cannot be assigned while a stream capture is running (the host-to-device "
+                               "copy cannot be recorded); assign them before the capture, or assign a number")
+        self._scale = vec
+        for (_, n), buf in self._scale_bufs.items():
+            if n == len(vec):
+                fenced_copy(buf, vec)
+            else:
+                fenced_fill(buf, float("nan"))
 
-    def scale_device(self, device):
-        if self._scale_dev is None or self._scale_dev.device != device:
-            self._scale_dev = torch.full((1,), float(self._scale), dtype=torch.float32, device=device)
-        return self._scale_dev
+    def scale_device(self, device, batch=None):
+        """The device values the kernels read, for a call of ``batch`` items: [1], or [batch] in the per-batch-item form (the ops pass the element count
+        on).  The buffer of a (device, length) is made once and never replaced."""
+        device = torch.device(device)
+        vec = self._scale if isinstance(self._scale, tuple) else None
+        if vec is not None and batch is not None and len(vec) != int(batch):
+            raise ValueError(f"IPAttnProcessor: scale holds {len(vec)} per-batch-item values, hidden_states has batch {int(batch)}")
+        if vec is not None:
+            n = len(vec)
+        else:
+            n = int(batch) if batch is not None and (device, int(batch)) in self._scale_bufs else 1
+        buf = self._scale_bufs.get((device, n))
+        if buf is None:
+            if device.type == "cuda" and vec is not None and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("IPAttnProcessor: the first call with per-batch-item scales of this length cannot run inside a stream capture (its "
+                                   "buffer is filled from the host); run it once eagerly first")
+            buf = (torch.tensor(vec, dtype=torch.float32).to(device) if vec is not None else
+                   torch.full((n,), float(self._scale), dtype=torch.float32, device=device))
+            self._scale_bufs[(device, n)] = buf
+        return buf
+
+    def scale_count(self, batch):
+        """how many values a call of ``batch`` items reads — 1, or ``batch`` once the per-batch-item form was used at that length (sticky: the [batch]
+        buffer stays) —: what the owner of a captured graph compares before it replays"""
+        batch = int(batch)
+        if batch <= 1:
+            return 1
+        if isinstance(self._scale, tuple):
+            return batch if len(self._scale) == batch else 1
+        return batch if any(n == batch for _, n in self._scale_bufs) else 1
 
     def _ip_weight(self):
         ws = (self.to_k_ip.weight, self.to_v_ip.weight)
@@ -725,7 +813,10 @@ class IPAttnProcessor(nn.Module):
             # rejects the shapes for every mask length, so there is no behaviour to reproduce
             raise RuntimeError("IPAttnProcessor: attention_mask cannot be combined with the decoupled text / image split "
                                "(the reference's baddbmm fails on the shapes as well)")
+        if return_attntion_probs or save_attn_to_dict is not None:
+            host_ip_scale(self, "the attention-map capture path")
         x, B, N, C, shape4 = _to_tokens(hidden_states)
+        self.scale_device(x.device, B)                       # a per-batch-item scale of another length than this batch: ValueError before any launch
         inner, heads, d = attn_dims(attn)
         xin = x
         if getattr(attn, "group_norm", None) is not None:
@@ -743,7 +834,7 @@ class IPAttnProcessor(nn.Module):
             norm = _fused_ln[0]
             wx, ux, vx = xq_weight(attn, norm)
             o = torch.empty((B * N, inner), dtype=x.dtype, device=x.device)
-            ops.xq_attn(x, wx, ux, vx, norm.eps, self.project_kv_xq(attn, enc, kv=kv_now), d, N, L, T, ip_scale=self.scale_device(x.device), out=o)
+            ops.xq_attn(x, wx, ux, vx, norm.eps, self.project_kv_xq(attn, enc, kv=kv_now), d, N, L, T, ip_scale=self.scale_device(x.device, B), out=o)
             return _finish(attn, o, B, N, C, shape4, xin, _fused_residual)
         if _fused_ln is not None:
             norm, rows = _fused_ln
@@ -754,7 +845,7 @@ class IPAttnProcessor(nn.Module):
         o = torch.empty((B * N, inner), dtype=x.dtype, device=x.device)
         ops.attention(q, inner, N * inner, k, inner, L * inner, vt, ldt, inner * ldt, L, B, heads, d, N, attn.scale,
                       o, inner, N * inner, k1=kip, k1_ld=inner, k1_bs=T * inner, vt1=vtip, vt1_ld=ldi, vt1_bs=inner * ldi,
-                      len1=T, w1=float(self.scale), w1_dev=self.scale_device(x.device))
+                      len1=T, w1=0.0 if isinstance(self.scale, tuple) else float(self.scale), w1_dev=self.scale_device(x.device, B))
         out = _finish(attn, o, B, N, C, shape4, xin, _fused_residual)
         if return_attntion_probs or save_attn_to_dict is not None:
             probs = _save_probs(attn, q, inner, k, inner, B, N, L, save_attn_to_dict, save_keys, attn_key,

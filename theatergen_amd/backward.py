@@ -22,7 +22,7 @@ import os
 import torch
 
 from . import ops
-from .attention_processor import AttnProcessor, IPAttnProcessor, tensor_version
+from .attention_processor import AttnProcessor, IPAttnProcessor, host_ip_scale, tensor_version
 from .unet import BasicTransformerBlock, DeviceSchedule, _Act  # noqa: F401
 from .weights_pack import pack_conv1x1, pack_conv3x3
 
@@ -155,7 +155,7 @@ def attention_input_grad(attn, proc, h2d, B, N, enc, dout, extra):
             et = enc[:, :L].contiguous().reshape(B * L, ctx)
             ei = enc[:, L:].contiguous().reshape(B * T, ctx)
             segs.append((ops.linear(et, attn.to_k.weight), ops.linear(et, attn.to_v.weight), L, 1.0, extra))
-            segs.append((ops.linear(ei, proc.to_k_ip.weight), ops.linear(ei, proc.to_v_ip.weight), T, float(proc.scale), None))
+            segs.append((ops.linear(ei, proc.to_k_ip.weight), ops.linear(ei, proc.to_v_ip.weight), T, host_ip_scale(proc, 'the attention reverse pass'), None))
         else:
             e2 = enc.contiguous().reshape(B * Ltot, ctx)
             segs.append((ops.linear(e2, attn.to_k.weight), ops.linear(e2, attn.to_v.weight), Ltot, 1.0, extra))
@@ -433,6 +433,11 @@ class UNetInputGrad:
         return loss, grad
 
 
+def ip_scale_forms(unet):
+    """per IP processor of ``unet``: 0 for a number, else the length of its per-batch-item scale — what a captured iteration bakes in besides weights"""
+    return tuple(len(p.scale) if isinstance(p.scale, tuple) else 0 for p in unet.attn_processors.values() if isinstance(p, IPAttnProcessor))
+
+
 class GraphedInputGrad:
     """``UNetInputGrad.loss_and_grad`` captured ONCE into a hipGraph and replayed: for callers that run many iterations with the same
     shapes, conditioning and loss function (the inner loop of ``latent_backward_guidance``: up to 5 iterations x 10 steps per image).
@@ -449,6 +454,9 @@ class GraphedInputGrad:
         # a PRIVATE static copy of the conditioning (the caller's tensor may be a temporary): what the captured launches' K / V^T caches belong to
         self.enc = unet.register_conditioning(encoder_hidden_states.detach().to(unet.dtype).clone().contiguous())
         args = (self.sample, self.timestep, self.enc, loss_fn, save_keys)
+        # the captured forward reads every IP processor's scale from its [1] device buffer (and the reverse pass takes it as a host constant): the graph
+        # is good for the NUMBER form only, and ``run`` looks before it replays
+        self._ip_forms = ip_scale_forms(unet)
         token = _STREAMS_OVERRIDE.set(int(streams))
         try:
             with torch.no_grad():
@@ -484,6 +492,10 @@ class GraphedInputGrad:
 
     def run(self, sample=None, timestep=None):
         """-> (loss, grad): the graph's static output tensors (overwritten by the next ``run``)."""
+        if ip_scale_forms(self.unet) != self._ip_forms:
+            raise RuntimeError("GraphedInputGrad: the form of an IPAttnProcessor.scale changed since the capture (a number then, per-batch-item values "
+                               "now, or the other way round); the captured launches read the buffer of the old form.  Assign a number (the reverse pass "
+                               "has no per-item scale) or build a new GraphedInputGrad")
         if sample is not None:
             self.sample.copy_(sample)
         if timestep is not None:
@@ -533,7 +545,8 @@ def latent_backward_guidance(adapter, scheduler, unet, cond_embeddings, index, b
         # the key is (shapes, dtypes, loss arguments, a weight / processor epoch) — NOT the identity of the conditioning tensor: a caller
         # that builds a fresh ``torch.cat`` per step gets its embeddings COPIED into the graph's static buffer (K / V^T re-projected in place);
         # an in-place weight update, a LoRA merge or ``set_attn_processor`` changes the epoch and re-captures (the graph bakes packed weights)
-        epoch = (sum(tensor_version(p_) or 0 for p_ in unet.parameters()), tuple(id(v) for v in unet.attn_processors.values()))
+        # (the form of the IP scale is part of it: a cache hit must never replay launches captured for a number under per-batch-item values)
+        epoch = (sum(tensor_version(p_) or 0 for p_ in unet.parameters()), tuple(id(v) for v in unet.attn_processors.values()), ip_scale_forms(unet))
         gkey = (tuple(latents.shape), str(unet.dtype), tuple(cond_embeddings.shape), str(cond_embeddings.dtype), repr(bboxes), repr(object_positions),
                 repr(keys), float(loss_scale), repr(sorted(kwargs.items())), epoch)
         gig = cache.get(gkey)

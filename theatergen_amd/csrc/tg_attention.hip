@@ -49,6 +49,7 @@ struct AttnParams {
   float scale_log2;
   float w1;
   const float* w1_dev;
+  int w1_stride;                 // 0: w1_dev is one float; 1: one float per batch item (tg_attention_ps)
   void* out; long out_ld, out_bs;
   int causal;
   const float* mask; long mask_bs, mask_hs, mask_qs;   // MASK instances: additive score bias mask[b*bs + h*hs + q*qs + key] (fp32, score units)
@@ -377,7 +378,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
         ps += e;
       }
     const float l1 = ps + __shfl_xor(ps, 32, 64);
-    const float f = (p.w1_dev != nullptr ? *p.w1_dev : p.w1) / l1;      // device scalar: the IP scale may change between replays of a captured graph
+    // device value: the IP scale may change between replays of a captured graph.  One float, or one per batch item (w1_stride = 1: `b` is the
+    // block's, so the load stays scalar); it enters as the same `w1 / l1` either way
+    const float f = (p.w1_dev != nullptr ? p.w1_dev[(long)b * p.w1_stride] : p.w1) / l1;
 #pragma unroll
     for (int kvt = 0; kvt < 2; ++kvt)
 #pragma unroll
@@ -504,7 +507,7 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(int b0, int heads, int 
 
 }  // namespace
 
-extern "C" int tg_attention(const tg_attn_desc* d, void* stream) {
+extern "C" int tg_attention_ps(const tg_attn_desc* d, int32_t ip_scale_count, void* stream) {
   TG_CHECK(d != nullptr, TG_ERR_ARG, "tg_attention: null descriptor");
   TG_CHECK(d->dtype == TG_BF16 || d->dtype == TG_F16, TG_ERR_ARG, "tg_attention: bad dtype");
   TG_CHECK(d->batch > 0 && d->heads > 0 && d->n_q > 0 && d->len0 > 0, TG_ERR_ARG, "tg_attention: empty problem");
@@ -515,6 +518,9 @@ extern "C" int tg_attention(const tg_attn_desc* d, void* stream) {
            "tg_attention: pitches must keep 16-byte alignment");
   TG_CHECK(d->len1 >= 0 && d->len1 <= KV, TG_ERR_ARG, "tg_attention: len1 (%d) must be <= 64", d->len1);
   if (d->len1 > 0) TG_CHECK(d->k1 && d->vt1 && d->k1_ld % 8 == 0 && d->vt1_ld % 8 == 0, TG_ERR_ARG, "tg_attention: bad segment 1");
+  TG_CHECK(ip_scale_count == 0 || ip_scale_count == 1 || ip_scale_count == d->batch, TG_ERR_ARG,
+           "tg_attention_ps: ip_scale_count = %d (0 or 1: w1_dev is one float; batch = %d: one per batch item)", ip_scale_count, d->batch);
+  TG_CHECK(ip_scale_count <= 1 || d->w1_dev != nullptr, TG_ERR_ARG, "tg_attention_ps: ip_scale_count = %d needs w1_dev", ip_scale_count);
   AttnParams p{};
   p.heads = d->heads; p.hd = d->head_dim; p.n_q = d->n_q;
   p.q = d->q; p.q_ld = d->q_ld; p.q_bs = d->q_bs;
@@ -523,6 +529,7 @@ extern "C" int tg_attention(const tg_attn_desc* d, void* stream) {
   p.scale_log2 = d->scale * 1.4426950408889634f;
   p.w1 = d->w1;
   p.w1_dev = d->w1_dev;
+  p.w1_stride = ip_scale_count > 1 ? 1 : 0;
   p.out = d->out; p.out_ld = d->out_ld; p.out_bs = d->out_bs;
   p.causal = d->causal;
   if (d->mask != nullptr) {
@@ -534,6 +541,8 @@ extern "C" int tg_attention(const tg_attn_desc* d, void* stream) {
   if (d->dtype == TG_BF16) return dispatch_attn<bf16_t>(d, p, st);
   return dispatch_attn<f16_t>(d, p, st);
 }
+
+extern "C" int tg_attention(const tg_attn_desc* d, void* stream) { return tg_attention_ps(d, 0, stream); }
 
 extern "C" int tg_attn_probs(int32_t dtype, int32_t batch, int32_t b0, int32_t heads, int32_t head_dim, int32_t n_q,
                              const void* q, int64_t q_ld, int64_t q_bs, const void* k, int64_t k_ld, int64_t k_bs,

@@ -57,10 +57,11 @@ struct GemmParams {
   int patch_pwl, patch_np;
   // cross-attention epilogue of the LayerNorm-folded to_q projection (gemm_glds_kernel<..., XA>, tg_xattn_epi.h, tg_xq_attn)
   const void* xa_kv;          // [batch][N / 160 tiles][pieces of 1 KiB]: K / V^T MFMA fragments of the tile's heads (tg_xq_kv_pack)
-  const float* xa_ip_scale;   // device scalar (IPAttnProcessor.scale) or NULL (1.0)
+  const float* xa_ip_scale;   // device scalar (IPAttnProcessor.scale), one per batch item (xa_ip_stride = 1, tg_xq_attn_ps) or NULL (1.0)
   int xa_rows_per_batch, xa_tiles_n, xa_L, xa_T;
   int slab_order;   // work order of the persistent kernels (GemmRoute::column_major): 0 tile-major; 1 slab conv (column tile, split)-major / row-tile-minor,
                     // ping-pong tiles column-major
+  int xa_ip_stride; // 0: xa_ip_scale[0] for every tile; 1: xa_ip_scale[the tile's batch item].  Sits in what was padding in front of gn_part: no field moves
   float* gn_part;   // two-wave slab conv, unsplit: GroupNorm partial sums of the output, fp32 [batch][hw / 64][N / gn_cpg][2] (tg_gemm_desc.out_gn_partials), or NULL
   int gn_cpg;       // ... channels per group (divides 80)
 };

@@ -136,7 +136,7 @@ extern "C" int tg_xq_kv_pack(int32_t dtype, int32_t batch, int32_t C, int32_t he
   return TG_OK;
 }
 
-extern "C" int tg_xq_attn(const tg_xq_attn_desc* d, void* stream) {
+extern "C" int tg_xq_attn_ps(const tg_xq_attn_desc* d, int32_t ip_scale_count, void* stream) {
   TG_CHECK(d != nullptr, TG_ERR_ARG, "tg_xq_attn: null descriptor");
   TG_CHECK(d->dtype == TG_BF16 || d->dtype == TG_F16, TG_ERR_ARG, "tg_xq_attn: dtype %d", d->dtype);
   TG_CHECK(d->x && d->wq && d->ln_u && d->ln_v && d->kv && d->out && d->ln_eps > 0.f, TG_ERR_ARG, "tg_xq_attn: null operand or eps <= 0");
@@ -153,6 +153,10 @@ extern "C" int tg_xq_attn(const tg_xq_attn_desc* d, void* stream) {
   TG_CHECK(d->ldx == d->C && d->ldc % 8 == 0 && d->ldc >= d->C, TG_ERR_ARG, "tg_xq_attn: x must be [M, C] contiguous, out pitch a multiple of 8");
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   TG_CHECK(al16(d->x) && al16(d->wq) && al16(d->ln_u) && al16(d->ln_v) && al16(d->kv) && al16(d->out), TG_ERR_ARG, "tg_xq_attn: operands must be 16-byte aligned");
+  TG_CHECK(ip_scale_count == 0 || ip_scale_count == 1 || ip_scale_count == d->M / d->rows_per_batch, TG_ERR_ARG,
+           "tg_xq_attn_ps: ip_scale_count = %d (0 or 1: ip_scale is one float; M / rows_per_batch = %lld: one per batch item)", ip_scale_count,
+           (long long)(d->M / d->rows_per_batch));
+  TG_CHECK(ip_scale_count <= 1 || d->ip_scale != nullptr, TG_ERR_ARG, "tg_xq_attn_ps: ip_scale_count = %d needs ip_scale", ip_scale_count);
   GemmParams p{};
   p.a0 = d->x; p.c0 = d->C; p.w = d->wq; p.M = d->M; p.N = d->C; p.K = d->C; p.lda = d->C; p.ldw = d->C;
   p.rows_per_batch = d->M; p.out = d->out; p.ldc = d->ldc; p.out_scale = 1.0f; p.act = TG_ACT_NONE;
@@ -161,7 +165,7 @@ extern "C" int tg_xq_attn(const tg_xq_attn_desc* d, void* stream) {
   const long tiles = (d->M / 128) * tiles_n;
   p.full_tiles = (int)tiles; p.tail_s = 1; p.tiles_n = tiles_n; p.tile_bm = 128; p.tile_bn = tw; p.kt_per_split = 0;
   p.epi_lds = 1;
-  p.xa_kv = d->kv; p.xa_ip_scale = d->ip_scale; p.xa_rows_per_batch = d->rows_per_batch; p.xa_tiles_n = tiles_n; p.xa_L = d->text_len; p.xa_T = d->ip_tokens;
+  p.xa_kv = d->kv; p.xa_ip_scale = d->ip_scale; p.xa_ip_stride = ip_scale_count > 1 ? 1 : 0; p.xa_rows_per_batch = d->rows_per_batch; p.xa_tiles_n = tiles_n; p.xa_L = d->text_len; p.xa_T = d->ip_tokens;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // tile count decides the instance like the planner's 128 x 160 rule: up to one round of 256 -> three K stages (one workgroup per CU), else two per CU;
   // head_dim 160 needs the three-stage instance (75 KiB of fragments per head); head_dim 64 follows the same rule as 80 (its 60 KiB fit two stages of 32 KiB)
@@ -177,6 +181,8 @@ extern "C" int tg_xq_attn(const tg_xq_attn_desc* d, void* stream) {
   if (d->head_dim == 80) return three ? launch_xq<f16_t, 3, 80>(p, (int)tiles, st) : launch_xq<f16_t, 2, 80>(p, (int)tiles, st);
   return launch_xq<f16_t, 3, 160>(p, (int)tiles, st);
 }
+
+extern "C" int tg_xq_attn(const tg_xq_attn_desc* d, void* stream) { return tg_xq_attn_ps(d, 0, stream); }
 
 namespace {
 }  // namespace

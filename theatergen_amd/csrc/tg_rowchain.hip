@@ -316,8 +316,9 @@ struct RcXattnParams {
   long M;
   int rows_per_batch;   // tokens per batch item (multiple of 32 * NW)
   float ln_eps;
-  const float* ip_scale;  // device scalar (IPAttnProcessor.scale) or NULL (1.0)
+  const float* ip_scale;  // device scalar (IPAttnProcessor.scale), one per batch item (ip_stride = 1, tg_rc_xattn_ps) or NULL (1.0)
   int dbg;                // always 0 (RC_DBG_RT): 1 no to_q MFMAs, 2 no attention, 4 no to_out MFMAs, 8 no stage DMA, 16 no barriers
+  int ip_stride;          // 0: ip_scale[0] for every workgroup; 1: ip_scale[the workgroup's batch item]
 };
 
 template <typename T> __device__ __forceinline__ typename Vec<T>::v8 pack8r(const f32x16& a, int r0) {
@@ -479,7 +480,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // ---- attention, one head per stage; O pieces overwrite the head's dead q pieces.  Per head a stream of 12 K fragments (key tile
   // major) and 12 V^T fragments (PV step major), each read 6 ahead of its MFMA; the V^T reads are issued before the softmax arithmetic.
   float w_ip = 1.0f;
-  if (IPT > 0 && p.ip_scale != nullptr) w_ip = *p.ip_scale;
+  if (IPT > 0 && p.ip_scale != nullptr) w_ip = p.ip_scale[bi * p.ip_stride];      // bi is the workgroup's: a scalar load either way
   const float NEG = -1.0e30f;
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
@@ -1775,7 +1776,7 @@ extern "C" int tg_rc_linear_dup(const tg_rc_linear_desc* d, int64_t c_dup_offset
   return launch_rc_linear<f16_t>(d, p, st);
 }
 
-extern "C" int tg_rc_xattn(const tg_rc_xattn_desc* d, void* stream) {
+extern "C" int tg_rc_xattn_ps(const tg_rc_xattn_desc* d, int32_t ip_scale_count, void* stream) {
   TG_CHECK(d != nullptr, TG_ERR_ARG, "tg_rc_xattn: null descriptor");
   TG_CHECK(d->dtype == TG_BF16 || d->dtype == TG_F16, TG_ERR_ARG, "tg_rc_xattn: dtype %d", d->dtype);
   TG_CHECK(d->h && d->wq && d->kv && d->wo && d->out && d->M > 0, TG_ERR_ARG, "tg_rc_xattn: null operand or M <= 0");
@@ -1784,13 +1785,20 @@ extern "C" int tg_rc_xattn(const tg_rc_xattn_desc* d, void* stream) {
   TG_CHECK(d->rows_per_batch > 0 && d->rows_per_batch % 128 == 0 && d->M % d->rows_per_batch == 0, TG_ERR_ARG,
            "tg_rc_xattn: rows_per_batch = %d must be a multiple of 128 that divides M (a workgroup's 128 tokens share one key set)", d->rows_per_batch);
   TG_CHECK(d->ldh >= 320 && d->ldh % 8 == 0 && d->ldc >= 320 && d->ldc % 8 == 0, TG_ERR_ARG, "tg_rc_xattn: row pitches");
+  TG_CHECK(ip_scale_count == 0 || ip_scale_count == 1 || ip_scale_count == d->M / d->rows_per_batch, TG_ERR_ARG,
+           "tg_rc_xattn_ps: ip_scale_count = %d (0 or 1: ip_scale is one float; M / rows_per_batch = %lld: one per batch item)", ip_scale_count,
+           (long long)(d->M / d->rows_per_batch));
+  TG_CHECK(ip_scale_count <= 1 || d->ip_scale != nullptr, TG_ERR_ARG, "tg_rc_xattn_ps: ip_scale_count = %d needs ip_scale", ip_scale_count);
   RcXattnParams p;
   p.h = d->h; p.ldh = d->ldh; p.wq = d->wq; p.kv = d->kv; p.wo = d->wo; p.out = d->out; p.ldc = d->ldc; p.M = d->M;
   p.rows_per_batch = d->rows_per_batch; p.ln_eps = d->ln_eps; p.ip_scale = d->ip_scale; p.dbg = 0;
+  p.ip_stride = ip_scale_count > 1 ? 1 : 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (d->dtype == TG_BF16) return dispatch_rc_xattn<bf16_t>(d, p, st);
   return dispatch_rc_xattn<f16_t>(d, p, st);
 }
+
+extern "C" int tg_rc_xattn(const tg_rc_xattn_desc* d, void* stream) { return tg_rc_xattn_ps(d, 0, stream); }
 
 extern "C" int tg_rc_kv_pack(int32_t dtype, int32_t batch, const void* k, const void* vt, int64_t ldt, int32_t text_len, const void* kip,
                              const void* vtip, int64_t ldi, int32_t ip_tokens, void* out, void* stream) {

@@ -62,7 +62,7 @@ __device__ __forceinline__ void xattn_epilogue(const GemmParams& p, f32x16 (&acc
     for (int r = 0; r < 16; ++r) acc[0][j][r] = 0.f;
   const long bi = m0 / p.xa_rows_per_batch;                      // the tile's batch item (uniform: rows_per_batch % 128 == 0)
   const char* blob = reinterpret_cast<const char*>(p.xa_kv) + (bi * p.xa_tiles_n + tile_n) * (long)(G::NPT * 1024);
-  const float ipw = p.xa_T > 0 ? (p.xa_ip_scale != nullptr ? *p.xa_ip_scale : 1.0f) : 0.f;
+  const float ipw = p.xa_T > 0 ? (p.xa_ip_scale != nullptr ? p.xa_ip_scale[bi * p.xa_ip_stride] : 1.0f) : 0.f;
   const int L = p.xa_L, Tn = p.xa_T;
 #pragma unroll
   for (int h = 0; h < G::HPT; ++h) {

@@ -140,6 +140,7 @@ class IPAdapter:
         return image_prompt_embeds, uncond_image_prompt_embeds
 
     def set_scale(self, scale):
+        """``scale``: the reference's number, or a 1-D sequence of per-batch-item values, handed to the processors as it is (``IPAttnProcessor.scale``)"""
         for attn_processor in self.pipe.unet.attn_processors.values():
             if isinstance(attn_processor, IPAttnProcessor):
                 attn_processor.scale = scale

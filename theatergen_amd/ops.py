@@ -276,11 +276,25 @@ def xq_kv_pack(k, vt, ldt, L, kip, vtip, ldi, T, batch, C_, head_dim, out=None):
     return out
 
 
+def _ip_scale_count(ip_scale, batch, who):
+    """Element count of a device IP scale: 1 (one value for the launch) or ``batch`` (one per batch item); anything else is refused here, before the library."""
+    if ip_scale is None:
+        return 0
+    if ip_scale.dtype != torch.float32 or not ip_scale.is_cuda or not ip_scale.is_contiguous():
+        raise RuntimeError(f"{who}: the IP scale must be a contiguous fp32 device tensor")
+    n = int(ip_scale.numel())
+    if n != 1 and n != int(batch):
+        raise RuntimeError(f"{who}: the IP scale has {n} elements, the launch takes 1 or its batch ({int(batch)})")
+    return n
+
+
 def xq_attn(x, wq, ln_u, ln_v, ln_eps, kv, head_dim, rows_per_batch, text_len, ip_tokens, ip_scale=None, out=None):
-    """norm2 + attn2.to_q + (decoupled text + image) cross-attention of an inner-level block in one launch -> O [M, C]; see tg_xq_attn"""
+    """norm2 + attn2.to_q + (decoupled text + image) cross-attention of an inner-level block in one launch -> O [M, C]; see tg_xq_attn.
+    ``ip_scale``: fp32 device tensor of 1 element or of M / rows_per_batch (one per batch item: tg_xq_attn_ps)."""
     from ._lib import XqAttnDesc
     _need_cuda(x)
     M, Cc = x.shape
+    n_ips = _ip_scale_count(ip_scale, M // max(int(rows_per_batch), 1), "xq_attn")
     assert x.stride(1) == 1 and x.stride(0) == Cc and wq.shape == (Cc, Cc)
     if out is None:
         out = torch.empty(M, Cc, dtype=x.dtype, device=x.device)
@@ -296,16 +310,20 @@ def xq_attn(x, wq, ln_u, ln_v, ln_eps, kv, head_dim, rows_per_batch, text_len, i
     # block; 80: 128 x 160 with a shared block) — the padded key slots and zero rows a tile multiplies are not counted as work
     flops = 2.0 * M * Cc * Cc + 4.0 * M * L_ * Cc
     tile = "128x128" if int(head_dim) == 64 else "128x160"
-    _profiled(lambda: _lib.check(_lib.lib().tg_xq_attn(C.byref(d), _stream())), f"gemm_glds_kernel<plain+ln+xattn d{head_dim},{tile}>", M, Cc, Cc, flops,
+    launch = ((lambda: _lib.check(_lib.lib().tg_xq_attn_ps(C.byref(d), n_ips, _stream()))) if n_ips > 1 else
+              (lambda: _lib.check(_lib.lib().tg_xq_attn(C.byref(d), _stream()))))
+    _profiled(launch, f"gemm_glds_kernel<plain+ln+xattn d{head_dim},{tile}>", M, Cc, Cc, flops,
               alg_bytes=2.0 * (2 * M * Cc + Cc * Cc) + 2.0 * (M // rows_per_batch) * 2 * L_ * Cc)
     return out
 
 
 def rc_xattn(h, wq, kv, wo, rows_per_batch, ln_eps, ip_tokens, ip_scale=None, out=None, text_len=77):
-    """norm2 + cross-attention (+ decoupled image keys) + to_out + residual in one launch; see tg_rc_xattn"""
+    """norm2 + cross-attention (+ decoupled image keys) + to_out + residual in one launch; see tg_rc_xattn.
+    ``ip_scale``: fp32 device tensor of 1 element or of M / rows_per_batch (one per batch item: tg_rc_xattn_ps)."""
     from ._lib import RcXattnDesc
     _need_cuda(h)
     M, Cc = h.shape
+    n_ips = _ip_scale_count(ip_scale, M // max(int(rows_per_batch), 1), "rc_xattn")
     assert Cc == 320 and h.stride(1) == 1
     if out is None:
         out = torch.empty(M, 320, dtype=h.dtype, device=h.device)
@@ -319,7 +337,9 @@ def rc_xattn(h, wq, kv, wo, rows_per_batch, ln_eps, ip_tokens, ip_scale=None, ou
     d.ln_eps = float(ln_eps)
     d.ip_scale = _ptr(ip_scale)
     # algorithmic work: to_q + to_out (2 x 2 M 320^2) + scores and PV over the real keys (4 M 320 (L + T))
-    _profiled(lambda: _lib.check(_lib.lib().tg_rc_xattn(C.byref(d), _stream())), f"rc_xattn_kernel<77+{int(ip_tokens)}>",
+    launch = ((lambda: _lib.check(_lib.lib().tg_rc_xattn_ps(C.byref(d), n_ips, _stream()))) if n_ips > 1 else
+              (lambda: _lib.check(_lib.lib().tg_rc_xattn(C.byref(d), _stream()))))
+    _profiled(launch, f"rc_xattn_kernel<77+{int(ip_tokens)}>",
               M, 320, 320, 4.0 * M * 320 * 320 + 4.0 * M * 320 * (int(text_len) + int(ip_tokens)), True,
               alg_bytes=2.0 * (3 * M * 320 + 2 * 320 * 320) + 2.0 * kv.numel())     # rows in, residual re-read, rows out; to_q, to_out; K / V^T fragments
     return out
@@ -462,7 +482,8 @@ def conv_up2(x, w_folded, batch, in_h, in_w, cin, bias=None, out=None):
 def attention(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale,
               out, out_ld, out_bs, k1=None, k1_ld=0, k1_bs=0, vt1=None, vt1_ld=0, vt1_bs=0, len1=0, w1=0.0, causal=False, w1_dev=None,
               mask=None):
-    """``w1_dev``: fp32 device scalar read by the kernel instead of the launch constant ``w1`` (graph-replayable IP scale).
+    """``w1_dev``: fp32 device tensor read by the kernel instead of the launch constant ``w1`` (graph-replayable IP scale): 1 element, or ``batch``
+    elements = one weight per batch item (tg_attention_ps).
     ``mask``: additive score bias, fp32 [Bm, Hm, Qm, len0] with Bm in {1, batch}, Hm in {1, heads}, Qm in {1, n_q} (size-1 dims broadcast)."""
     _need_cuda(q)
     d = AttnDesc()
@@ -478,9 +499,11 @@ def attention(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch,
     d.scale, d.w1 = float(scale), float(w1)
     d.out, d.out_ld, d.out_bs = _ptr(out), int(out_ld), int(out_bs)
     d.causal = 1 if causal else 0
+    n_w1 = 0
     if w1_dev is not None:
         if w1_dev.dtype != torch.float32 or not w1_dev.is_cuda:
             raise RuntimeError("attention: w1_dev must be an fp32 device tensor")
+        n_w1 = _ip_scale_count(w1_dev, batch, "attention")
         d.w1_dev = w1_dev.data_ptr()
     if mask is not None:
         if mask.dtype != torch.float32 or not mask.is_cuda or mask.ndim != 4 or not mask.is_contiguous() or mask.shape[3] != len0:
@@ -492,13 +515,15 @@ def attention(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch,
         d.mask_bs = hm * qm * len0 if bm > 1 else 0
         d.mask_hs = qm * len0 if hm > 1 else 0
         d.mask_qs = len0 if qm > 1 else 0
+    launch = ((lambda: _lib.check(_lib.lib().tg_attention_ps(C.byref(d), n_w1, _stream()))) if n_w1 > 1 else
+              (lambda: _lib.check(_lib.lib().tg_attention(C.byref(d), _stream()))))
     if _gemm_profile is None:
-        _lib.check(_lib.lib().tg_attention(C.byref(d), _stream()))
+        launch()
         return out
     # profiling mode (bench.py roofline leg): HIP events around this launch; algorithmic flops = QK^T + PV of both segments, no padding
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    _lib.check(_lib.lib().tg_attention(C.byref(d), _stream()))
+    launch()
     e1.record()
     keys = int(len0) + int(len1)
     _gemm_profile.append(dict(kernel=f"attention_kernel<d{int(head_dim)},{'self' if int(len0) == int(n_q) else 'cross'}>", splits=1,

@@ -17,7 +17,7 @@ from collections import namedtuple
 import torch
 
 from . import ops
-from .attention_processor import register_replay_stream, tensor_version, unregister_replay_stream
+from .attention_processor import IPAttnProcessor, register_replay_stream, scale_vector, tensor_version, unregister_replay_stream
 from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler
 from .unet import DeviceSchedule
 
@@ -205,6 +205,23 @@ class DenoiseEngine:
         self.step_noise.copy_(table.reshape(self.step_noise.shape))
         self._noise_set = True
 
+    def _ip_processors(self):
+        return [p for p in self.unet.attn_processors.values() if isinstance(p, IPAttnProcessor)]
+
+    def set_ip_scale(self, scales):
+        """The IP-Adapter scale of the engine's images: one number (every image, the reference's ``set_scale``) or ``n_img`` values, one per image — the
+        reference generates a character whose database PNG exists at 0.4 and a first appearance at 0 (models/pipelines.py:183-199), and a batch of
+        characters mixes the two.  Per-image values are written as ``[s ; s]`` to every IP processor of the UNet, unconditional half first: ``set_scale``
+        covers both halves of the classifier-free-guidance batch.  New VALUES replay the captured step (the kernels read them from the device); going
+        from the one-value form to the per-image form, or to another ``n_img``, re-captures it once (``_signature``)."""
+        vec = scale_vector(scales)
+        if vec is not None:
+            if len(vec) != self.n_img:
+                raise ValueError(f"set_ip_scale: {len(vec)} values for an engine of n_img = {self.n_img} (one number, or one value per image)")
+            scales = vec + vec
+        for p in self._ip_processors():
+            p.scale = scales
+
     def _refresh_kv(self):
         self.unet.register_conditioning(self.enc)              # cache keyed by the tensor OBJECT self.enc (never its address)
 
@@ -276,11 +293,29 @@ class DenoiseEngine:
                               history=self.history, model_in=self.model_in)
 
     def _signature(self):
-        """Launch constants baked into a captured graph: the frozen-mask configuration and the guidance scale.  The IP scales
-        are NOT among them: ``IPAttnProcessor.scale`` is read from a device scalar by the attention kernel, so
+        """Launch constants baked into a captured graph: the frozen-mask configuration and the guidance scale.  The IP scale VALUES
+        are NOT among them: ``IPAttnProcessor.scale`` is read from device memory by the attention kernel, so
         ``IPAdapter.set_scale`` between characters (reference pipelines.py:196, 213) and the per-step gating of
-        ``ip_adapter/custom_pipelines.py:328-333`` replay the same graph."""
-        return self.frozen is not None, self.frozen_steps, self.g
+        ``ip_adapter/custom_pipelines.py:328-333`` replay the same graph.  Their FORM is: per IP processor, how many values a step of this batch
+        reads (``scale_count``: 1, or 2 n_img once ``set_ip_scale`` was given per-image values) is baked into the captured launches, and with it which
+        of the processor's buffers they read (one per length, never freed or moved), so a change of it re-captures.  A per-batch-item scale of
+        another length than this engine's batch (another engine's, on a shared UNet) has no meaning here: ValueError."""
+        procs, B = self._ip_processors(), 2 * self.n_img
+        for p in procs:
+            if isinstance(p.scale, tuple) and len(p.scale) != B:
+                raise ValueError(f"DenoiseEngine (n_img = {self.n_img}): an IP processor of the UNet holds {len(p.scale)} per-batch-item scales, a step "
+                                 f"of this engine has batch {B}; call set_ip_scale on THIS engine (or assign a number) before running it")
+        ip_form = tuple(p.scale_count(B) for p in procs)
+        return self.frozen is not None, self.frozen_steps, self.g, ip_form
+
+    def _check_replayable(self):
+        """after a ``before_step`` hook, before the replay it precedes: what the captured step baked in must still hold.  A hook may assign new VALUES
+        (numbers, or vectors of the form the step was captured in); one that changes the form — per-image scales on an engine captured with a number,
+        a vector of another length — would have the replay read a buffer the new values were not written to."""
+        if self.use_graph and self._signature() != self._graph_sig:
+            raise RuntimeError("DenoiseEngine: a before_step hook changed what the captured step bakes in (the FORM of the IP scale: one number / one "
+                               "value per image, or the frozen-mask / guidance constants); the replay would not see it.  Put the engine into that "
+                               "form before run() — set_ip_scale([...]) — and let the hook assign values of the same form")
 
     def _reset(self, latents):
         self.latents.copy_(latents.to(device=self.dev, dtype=torch.float32))
@@ -316,9 +351,11 @@ class DenoiseEngine:
         stream per engine: the second chain's kernels fill the partially filled grid rounds, small-grid layers and
         launch gaps of the first (+4 % images/s for 2 x 4 images vs 1 x 8 on MI355X).  Engines may share one UNet; each
         has its own conditioning buffers, K / V^T caches, kernel scratch slot and captured graph.  Returns the histories.
-        The IP scale is ONE device scalar per processor (= per UNet).  ``before_step(i)`` (optional) runs on the host before round i of replays is
-        queued — the per-step ``set_scale`` gating of ``ip_adapter/custom_pipelines.py:328-333``: the assignment fences its 4-byte fill against the
-        engine streams (``attention_processor.fenced_fill``), so round i - 1 still reads the old value and round i the new one."""
+        The IP scale lives with the processor (= per UNet): one number, or one value per batch item of the step (``set_ip_scale``; engines that share
+        a UNet then need the same ``n_img``).  ``before_step(i)`` (optional) runs on the host before round i of replays is queued — the per-step
+        ``set_scale`` gating of ``ip_adapter/custom_pipelines.py:328-333``: the assignment fences its write (a fill, or the copy of a vector) against
+        the engine streams (``attention_processor.fenced_fill`` / ``fenced_copy``), so round i - 1 still reads the old values and round i the new ones.
+        A hook may change VALUES, not the form the steps were captured in (RuntimeError before the round is queued)."""
         dev = engines[0].dev
         with torch.no_grad():
             for e, lat in zip(engines, latents_list):
@@ -334,6 +371,8 @@ class DenoiseEngine:
             for i in range(engines[0].steps):
                 if before_step is not None:
                     before_step(i)
+                    for e in engines:
+                        e._check_replayable()
                 for e, st in zip(engines, streams):
                     with torch.cuda.stream(st):
                         e.graph.replay()
@@ -351,8 +390,9 @@ class DenoiseEngine:
     def run(self, latents, before_step=None):
         """latents [n_img, C, h, w] (any float dtype / device) -> latents_all fp32 [steps+1, n_img, C, h, w] on the GPU.
         ``before_step(i)`` (optional) runs on the host before step i is launched — the place of the per-step
-        ``set_scale(0.0)`` / ``set_scale(s)`` gating of reference ``ip_adapter/custom_pipelines.py:328-333``; the IP scale is a
-        device scalar, so the same captured graph replays whatever it is set to."""
+        ``set_scale(0.0)`` / ``set_scale(s)`` gating of reference ``ip_adapter/custom_pipelines.py:328-333``; the IP scale is read from
+        device memory, so the same captured graph replays whatever VALUES it is set to.  A hook that changes its FORM (per-image values on an engine
+        captured with one number, a vector of another length) raises RuntimeError before the step is replayed: ``set_ip_scale`` comes before ``run``."""
         if self.kind == "euler_a" and not self._noise_set:
             raise RuntimeError("DenoiseEngine (Euler ancestral): set_step_noise(...) before run(): the step noise is drawn on the host in the reference's order")
         with torch.no_grad():
@@ -361,6 +401,7 @@ class DenoiseEngine:
             for i in range(self.steps):
                 if before_step is not None:
                     before_step(i)
+                    self._check_replayable()
                 if self.use_graph:
                     self.graph.replay()
                 else:
@@ -372,8 +413,11 @@ def denoise_single_object(adapter, prompt_embeds, negative_prompt_embeds, input_
                           image_prompt_embeds=None, uncond_image_prompt_embeds=None, num_inference_steps=50,
                           guidance_scale=7.5, engine=None):
     """Stage-1 per-character generation core (reference ``generate_semantic_guidance`` SD-1.5 branch, :183-247 image
-    prompt + scale, :369-453 loop, :488 stack): returns ``(latents [1,C,h,w], latents_all [steps+1,1,C,h,w])``."""
-    adapter.set_scale(scale)
+    prompt + scale, :369-453 loop, :488 stack): returns ``(latents [1,C,h,w], latents_all [steps+1,1,C,h,w])``.  ``scale``: one number, or one value
+    per row of ``prompt_embeds`` (a batch of characters, each at its own IP scale: ``DenoiseEngine.set_ip_scale``)."""
+    per_image = scale_vector(scale)
+    if per_image is None:
+        adapter.set_scale(scale)
     if image_prompt_embeds is None:
         image_prompt_embeds, uncond_image_prompt_embeds = adapter.get_image_embeds(clip_image_embeds=clip_image_embeds)
     enc = prepare_ip_embeds(prompt_embeds.to(adapter.pipe.unet.dtype), negative_prompt_embeds.to(adapter.pipe.unet.dtype),
@@ -383,6 +427,8 @@ def denoise_single_object(adapter, prompt_embeds, negative_prompt_embeds, input_
         engine = DenoiseEngine(adapter.pipe.unet, adapter.pipe.scheduler, n_img=n, height=input_latents.shape[-2] * 8,
                                width=input_latents.shape[-1] * 8, num_inference_steps=num_inference_steps,
                                guidance_scale=guidance_scale, enc_len=enc.shape[1])
+    if per_image is not None:
+        engine.set_ip_scale(per_image)
     engine.set_conditioning(enc)
     latents_all = engine.run(input_latents)
     return latents_all[-1], latents_all
@@ -499,6 +545,84 @@ def generate_semantic_guidance(task, fg_seed_now, basever, ip_prompt, database_p
         allv = hist.to(latents.dtype).clone()
         ret.append(allv.cpu() if offload_latents_to_cpu else allv)
     return tuple(ret)
+
+
+def generate_characters(task, fg_seeds, basever, ip_prompts, database_path, adapter, latents, num_inference_steps, obj_ids, guidance_scale=7.5,
+                        fast_after_steps=None, fast_rate=2, save_all_latents=False, offload_latents_to_cpu=True):
+    """Stage 1 of the non-XL branches for a LIST of characters in ONE engine run — what ``generate_semantic_guidance`` does once per character
+    (reference ``models/pipelines.py:175-490``), with the characters in the batch dimension of the captured step.  ``ip_prompts`` / ``obj_ids`` /
+    ``fg_seeds``: one entry per character; ``latents`` [n, C, h, w]: their initial latents (the reference draws them before the call and ``fg_seeds``
+    play no further part in its non-XL branch: they are only checked for length).
+
+    Per character, on the host, as in the reference: the database PNG and IP scale 0.4 — or the placeholder and scale 0 for a first appearance
+    (:183-199) —, the prompt prefix (:216-225), ``adapter.get_image_embeds`` and ``adapter.pipe.encode_prompt``.  Then ONE ``set_ip_scale`` with the
+    list of scales (the kernels read each image's own value), ONE ``run``, one decode per image, and each first appearance is saved as its reference
+    PNG (:476-477).  Afterwards the adapter's scale is the LAST character's number, as after the reference's loop over the same characters.  Returns a list with, per character, the tuple ``generate_semantic_guidance`` returns for it: ``(latents [1, C, h, w], image[,
+    latents_all [steps + 1, 1, C, h, w]])``.
+
+    Refused: ``basever='xl'`` (its stage 1 draws its own latents: NotImplementedError); two entries with the same ``obj_id`` and no PNG yet
+    (ValueError: one at a time, the second would have been generated with the first's image as its reference)."""
+    from PIL import Image
+    from . import schedule as tg_schedule
+    if basever == "xl":
+        raise NotImplementedError("generate_characters: the SDXL stage 1 draws its own latents per character (models/pipelines.py:251-300); "
+                                  "run generate_semantic_guidance(..., basever='xl') per character")
+    n = len(obj_ids)
+    if n == 0 or len(ip_prompts) != n or len(fg_seeds) != n or latents.shape[0] != n:
+        raise ValueError(f"generate_characters: {n} obj_ids, {len(ip_prompts)} ip_prompts, {len(fg_seeds)} fg_seeds, latents batch {latents.shape[0]}: "
+                         "one entry per character")
+    if any(not o for o in obj_ids):
+        raise RuntimeError("generate_characters: every character needs an obj_id (models/pipelines.py:183-233)")
+    unet = _own_unet(adapter, "generate_characters")
+    images_in, scales, new = [], [], []
+    for o in obj_ids:
+        try:
+            images_in.append(Image.open(database_path + str(o) + ".png"))
+            scales.append(0.4)
+            new.append(False)
+        except (OSError, ValueError):
+            if any(isnew and str(prev) == str(o) for prev, isnew in zip(obj_ids, new)):
+                raise ValueError(f"generate_characters: obj_id {o!r} appears twice and has no reference image yet ({database_path + str(o)}.png): in the "
+                                 "reference the second generation uses the first's image; generate them in two calls") from None
+            images_in.append(None)
+            scales.append(0)
+            new.append(True)
+    if any(new):
+        placeholder = Image.open(PLACEHOLDER_IMAGE)
+        images_in = [placeholder if im is None else im for im in images_in]
+    prefix = "single object, " if task == "editing" else "full-body picture of "
+    rows = [_text_and_image_rows(adapter, prefix + str(p), SINGLE_OBJECT_NEGATIVE_PROMPT, im) for p, im in zip(ip_prompts, images_in)]     # each [2, L, D]
+    enc = torch.cat([r[:1] for r in rows] + [r[1:] for r in rows], dim=0)                       # negatives first
+    scheduler = adapter.pipe.scheduler
+    timesteps = None
+    if fast_after_steps is not None:
+        scheduler.set_timesteps(num_inference_steps)
+        timesteps = tg_schedule.get_fast_schedule(scheduler.timesteps, fast_after_steps, fast_rate)
+    h8, w8 = latents.shape[-2], latents.shape[-1]
+    eng = _engine_of(adapter, n_img=n, height=8 * h8, width=8 * w8, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                     enc_len=enc.shape[1], timesteps=timesteps)
+    eng.set_ip_scale(scales)
+    eng.set_conditioning(enc.to(eng.dev, eng.dt))
+    hist = eng.run(latents)
+    # what the reference's loop over these characters leaves behind: the LAST character's number (queued after the replays; the per-image buffer keeps
+    # its length, so the next call replays the same graph).  The paths that take the scale as a host constant — stage-2 guidance: attention-map
+    # capture, the reverse pass — refuse a vector; they must find a number on this UNet afterwards, as after generate_semantic_guidance
+    adapter.set_scale(scales[-1])
+    out = hist[-1].to(unet.dtype)
+    vae = adapter.pipe.vae
+    post = getattr(getattr(adapter.pipe, "image_processor", None), "postprocess", None)
+    results = []
+    for i, o in enumerate(obj_ids):
+        decoded = vae.decode(out[i:i + 1] / vae.config.scaling_factor, return_dict=False)[0].detach()
+        image = post(decoded, output_type="pil", do_denormalize=[True])[0] if post is not None else _to_pil(decoded)
+        if new[i]:
+            image.save(database_path + str(o) + ".png")
+        ret = [out[i:i + 1], image]
+        if save_all_latents:
+            allv = hist[:, i:i + 1].to(latents.dtype).clone()
+            ret.append(allv.cpu() if offload_latents_to_cpu else allv)
+        results.append(tuple(ret))
+    return results
 
 
 def _check_xl_stage1(adapter):

@@ -9,7 +9,8 @@ Per dialogue d, turn tau in 1..4, character c in {0, 1}: one stage-1 character g
   * text embeddings ``randn(1, 77, D) * 0.5`` seeded by (d, tau, c); negative-prompt embeddings seeded once (shared),
   * image tokens ``randn(1, T, D) * 0.5`` seeded by the CHARACTER id (shared across turns: the broadcast payload);
     uncond image tokens seeded once,
-  * IP scale 0.4, guidance 7.5, 50 DDIM steps.
+  * IP scale 0.4, guidance 7.5, 50 DDIM steps.  ``story_jobs(..., ip_scales=)`` marks first appearances (the reference generates those at scale 0,
+    models/pipelines.py:183-199); ``job_ip_scales`` is the list ``DenoiseEngine.set_ip_scale`` takes.
 """
 from dataclasses import dataclass
 
@@ -29,6 +30,7 @@ class CharacterJob:
     dialogue: int
     turn: int
     char: int
+    ip_scale: float = 0.4                               # 0.4: the character's database image exists; 0: first appearance (placeholder image)
 
     @property
     def char_id(self):
@@ -43,8 +45,24 @@ class CharacterJob:
         return self.dialogue * 100 + self.turn          # seed_offset per (dialogue, turn)
 
 
-def story_jobs(dialogue, turns=4, chars=2):
-    return [CharacterJob(dialogue, t, c) for t in range(1, turns + 1) for c in range(chars)]
+def story_jobs(dialogue, turns=4, chars=2, ip_scales=None):
+    """``ip_scales``: None = every job at 0.4 (uniform); "first" = a character's first turn at 0, its later turns at 0.4 (the reference's stage 1);
+    or one value per job, turn-major."""
+    jobs = [CharacterJob(dialogue, t, c) for t in range(1, turns + 1) for c in range(chars)]
+    if ip_scales is None:
+        return jobs
+    if isinstance(ip_scales, str):
+        if ip_scales != "first":
+            raise ValueError(f"story_jobs: ip_scales = {ip_scales!r} (None, 'first' or one value per job)")
+        ip_scales = [0.0 if j.turn == 1 else 0.4 for j in jobs]
+    if len(ip_scales) != len(jobs):
+        raise ValueError(f"story_jobs: {len(ip_scales)} ip_scales for {len(jobs)} jobs")
+    return [CharacterJob(j.dialogue, j.turn, j.char, float(s)) for j, s in zip(jobs, ip_scales)]
+
+
+def job_ip_scales(jobs):
+    """per-image IP scales of a batch of jobs, in batch order"""
+    return [j.ip_scale for j in jobs]
 
 
 def _randn(shape, seed, scale=0.5):

@@ -563,6 +563,28 @@ int tg_add_noise(const float* x0, const float* noise, const float* ca, const flo
 int tg_masked_compose(float* dst, const float* src, const float* mask, int64_t planes, int32_t hw, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The image boundary (csrc/tg_image.hip): images cross the device boundary as uint8 RGB, HWC.  Additive to ABI 308: two new symbols,
+ * TG_ABI_VERSION unchanged.  Both are correct for every h, w >= 1 and any base alignment; with h * w % 4 == 0 and aligned bases (uint8 side 4 bytes,
+ * float side 4 elements) a thread moves 12 interleaved bytes and one 4-element unit per channel plane, otherwise one pixel.
+ *
+ * tg_image_from_u8: src uint8 [batch, h, w, 3] -> dst NCHW [copies * batch, 3, h, w] in dst_dtype (TG_BF16, TG_F16 or 2 = fp32); copy r of image b
+ *   is image r * batch + b (the `cat([x] * copies)` layout of a classifier-free-guidance batch).  Per element, in fp32:
+ *       v = float(u) / 255.0f        an IEEE division (NOT u * (1 / 255): the two differ for 126 of the 256 byte values)
+ *       range_mode 0: v              the ControlNet control image in [0, 1]     (models/pipelines.py:712-722, prepare_image)
+ *       range_mode 1: 2.0f * v - 1   the VAE encoder input in [-1, 1]           (models/pipelines.py:617-620)
+ *   then ONE round-to-nearest-even to dst_dtype: bit-equal to the host expression followed by `.to(dtype)`.
+ *   TG_ERR_ARG: copies < 1, a range_mode other than 0 / 1, a bad dtype, a null pointer, src == dst, batch / h / w < 1.
+ *
+ * tg_image_to_u8: src NCHW [batch, 3, h, w] in src_dtype (TG_BF16, TG_F16 or 2 = fp32) -> dst uint8 [batch, h, w, 3].  Per element: widen to fp32;
+ *   y = x * 0.5f + 0.5f; clamp to [0, 1]; p = y * 255.0f rounded once to fp32; rintf(p) (ties to even, numpy's `.round()`); convert to uint8 —
+ *   bit-equal to `((img.float() / 2 + 0.5).clamp(0, 1).cpu().permute(0, 2, 3, 1).numpy() * 255).round().astype("uint8")` (models/pipelines.py:163-173,
+ *   852-854).  +inf gives 255, -inf gives 0.  NaN has no reference value (numpy's `astype` of NaN is undefined): this kernel stores 0.
+ *   TG_ERR_ARG: a bad dtype, a null pointer, src == dst, batch / h / w < 1. */
+int tg_image_from_u8(const void* src, int32_t batch, int32_t h, int32_t w, int32_t range_mode, int32_t copies, void* dst, int32_t dst_dtype,
+                     void* stream);
+int tg_image_to_u8(const void* src, int32_t src_dtype, int32_t batch, int32_t h, int32_t w, void* dst, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-box guidance reductions (utils/guidance.py:91-148, 223-233) on an attention map
  * attn fp32 [heads, hw, n_tok]; mask fp32 [hw] (box mask).  One (token) column per call-row:
  * tg_guidance_topk: for each head: fg = mean(topk_{k_fg}(A*M)), bg = mean(topk_{k_bg}(A*(1-M)));

@@ -183,6 +183,8 @@ SIGNATURES = {
     "tg_masked_compose": (i32, [vp, vp, vp, i64, i32, vp]),
     "tg_gaussian_sample": (i32, [vp, vp, i32, i32, i32, f32, vp, vp]),
     "tg_add_noise": (i32, [vp, vp, vp, vp, i32, i64, vp, vp]),
+    "tg_image_from_u8": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, vp]),
+    "tg_image_to_u8": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "tg_guidance_topk": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, f32, f32, f32, vp, vp, vp]),
     "tg_guidance_ratio": (i32, [vp, i32, i32, i32, i32, vp, f32, vp, vp, vp]),
     "tg_guidance_ref": (i32, [vp, i32, i32, i32, i32, vp, vp, f32, f32, vp, vp, vp]),

@@ -166,6 +166,10 @@ HOT_GATES = [
     # the step epilogue, one body for every sampler (tg_step.hip; <DdimUpdate>, <SigmaUpdate>, <DpmUpdate>).  40 VGPRs is the largest of the three
     # hand-written kernels it replaced (22 / 40 / 22): a policy that pushes the shared body past that, or into scratch, has changed more than its arithmetic
     ("step_epilogue_kernel<", 0, 40),
+    # the uint8 <-> NCHW image boundary (tg_image.hip; <T, PX>): the 12-byte interleave of four pixels is register shuffling — scratch would mean the
+    # per-thread value arrays were indexed at run time
+    ("image_from_u8_kernel<", 0, 64),
+    ("image_to_u8_kernel<", 0, 64),
 ]
 
 

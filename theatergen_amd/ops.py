@@ -965,6 +965,45 @@ def scale_repeat(x, scale, copies, out=None):
     return out
 
 
+def image_from_u8(images, dtype, range_mode=1, copies=1, out=None):
+    """uint8 RGB ``[B, H, W, 3]`` on the device -> NCHW ``[copies * B, 3, H, W]`` in ``dtype`` (bf16 / fp16 / fp32); copy r of image b is row ``r * B + b``
+    (``cat([x] * copies)``).  ``range_mode`` 1: ``2 * (u / 255) - 1`` (VAE encoder input), 0: ``u / 255`` (ControlNet control image); fp32 arithmetic with
+    an IEEE division, one rounding to ``dtype``: bit-equal to ``torch.from_numpy(a.astype(np.float32) / 255.0)`` [``* 2.0 - 1.0``] ``.permute(0, 3, 1, 2)
+    .to(dtype)``."""
+    _need_cuda(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+        raise ValueError(f"image_from_u8: uint8 [B, H, W, 3] expected, got {images.dtype} {tuple(images.shape)}")
+    if dtype not in _SRC:
+        raise RuntimeError(f"theatergen_amd: image_from_u8 writes bf16 / fp16 / fp32, not {dtype}")
+    if int(copies) < 1:
+        raise ValueError(f"image_from_u8: copies must be >= 1, got {copies}")
+    B, H, W, _ = images.shape
+    images = images.contiguous()
+    shape = (int(copies) * B, 3, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=images.device)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError(f"image_from_u8: out must be a contiguous {dtype} tensor of shape {shape}")
+    _lib.check(_lib.lib().tg_image_from_u8(_ptr(images), B, H, W, int(range_mode), int(copies), _ptr(out), _SRC[dtype], _stream()))
+    return out
+
+
+def image_to_u8(images, out=None):
+    """NCHW ``[B, 3, H, W]`` (bf16 / fp16 / fp32) in [-1, 1] -> uint8 RGB ``[B, H, W, 3]`` on the device: bit-equal to ``((x.float() / 2 + 0.5).clamp(0, 1)
+    .permute(0, 2, 3, 1).numpy() * 255).round().astype("uint8")`` (ties to even; NaN, which has no value there, gives 0)."""
+    _need_cuda(images)
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype not in _SRC:
+        raise ValueError(f"image_to_u8: bf16 / fp16 / fp32 [B, 3, H, W] expected, got {images.dtype} {tuple(images.shape)}")
+    B, _, H, W = images.shape
+    images = images.contiguous()
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=images.device)
+    elif tuple(out.shape) != (B, H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError(f"image_to_u8: out must be a contiguous uint8 tensor of shape {(B, H, W, 3)}")
+    _lib.check(_lib.lib().tg_image_to_u8(_ptr(images), _SRC[images.dtype], B, H, W, _ptr(out), _stream()))
+    return out
+
+
 def blend_latents(bg, fg, mask, ratio, sigma=1.0, storage_dtype=None):
     """fp32 in / out; ``storage_dtype`` torch.float16 / torch.bfloat16: reproduce the half-precision roundings of the
     reference expression (its latents are ``unet.dtype`` tensors)"""

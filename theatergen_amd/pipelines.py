@@ -846,6 +846,103 @@ def final_image_generation(basever, processor, controlnetpipe, tpipe, overall_pr
 
 
 @torch.no_grad()
+def generate_final_images(basever, processor, controlnetpipe, overall_prompts, overall_negative_prompts, single_obj_img_lists, height, width, bg_seeds,
+                          inp_masks, input_imgs, adapter, latents_all_list, input_embeddings_list, num_inference_steps, frozen_steps, guidance_scale=7.5):
+    """Stage 2 of the non-XL branches for a LIST of turns in ONE engine run — what ``final_image_generation`` does once per turn (reference
+    ``models/pipelines.py:592-857``; the caller's loop ``theatergen.py:448-484`` needs nothing from one turn in the next), with the turns in the batch
+    dimension of the captured ControlNet + UNet step.  One entry per turn in every list; returns a list with, per turn, the pair
+    ``final_image_generation`` returns for it: ``(latents [1, C, h, w], images uint8 ndarray [1, H, W, 3])``.
+
+    Per turn, on the host, as in the single call: the frozen mask from ``inp_masks[i]``, ``processor(np.array(input_imgs[i]))`` and the control
+    image preparation, the conditioning rows of ``overall_prompts[i]`` with the image tokens of ``single_obj_img_lists[i][0]``; the three random
+    draws (posterior noise, re-noising noise, background latents) come from ``torch.Generator(device).manual_seed(bg_seeds[i])`` in the reference's
+    order with the single call's shapes and dtype, so they are bit-equal to what the single call draws for that turn alone.
+    ``latents_all_list[i]`` is overwritten as the single call overwrites ``latents_all`` (row 0 the background noise, rows 1.. the frozen rows).
+    IP scale 0.1 as one number.  Shared by the turns: one upload of the pasted images as uint8 HWC and one ``tg_image_from_u8``, one VAE encode,
+    one ``add_noise``, one engine (``n_img`` = the number of turns; rows ``[neg_0 .. neg_{n-1} ; pos_0 .. pos_{n-1}]``), one ``run``, one VAE decode,
+    one ``tg_image_to_u8`` and one device-to-host copy of ``[n, H, W, 3]`` bytes.
+
+    Refused before any device work or side effect: ``basever='xl'`` (NotImplementedError: its stage 2 runs another UNet, scheduler and adapter, run
+    ``final_image_generation(..., basever='xl')`` per turn); lists of unequal length or an empty list, turns whose images, masks, text embeddings or
+    ``latents_all`` differ in shape (ValueError); a foreign ControlNet / UNet (TypeError, the single call's messages).  The LENGTH of the conditioning
+    rows (text + image tokens) and the size of the prepared control images are only known once every turn's ``encode_prompt`` / ``get_image_embeds`` /
+    ``processor`` has run: turns that differ there are a ValueError after that per-turn work, still before ``set_scale``, the ``latents_all_list``
+    writes and the engine."""
+    import numpy as np
+    if basever == "xl":
+        raise NotImplementedError("generate_final_images: the SDXL stage 2 runs controlnetpipe.unet with a T2I-Adapter and Euler-ancestral steps "
+                                  "(models/pipelines.py:654-700); run final_image_generation(..., basever='xl') per turn")
+    lists = {"overall_prompts": overall_prompts, "overall_negative_prompts": overall_negative_prompts, "single_obj_img_lists": single_obj_img_lists,
+             "bg_seeds": bg_seeds, "inp_masks": inp_masks, "input_imgs": input_imgs, "latents_all_list": latents_all_list,
+             "input_embeddings_list": input_embeddings_list}
+    n = len(overall_prompts)
+    if n == 0 or any(len(v) != n for v in lists.values()):
+        raise ValueError("generate_final_images: " + ", ".join(f"{len(v)} {k}" for k, v in lists.items()) + ": one entry per turn, at least one turn")
+    pasted = [np.asarray(im) for im in input_imgs]
+    if any(a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 for a in pasted):
+        raise ValueError("generate_final_images: every input image must be uint8 RGB [H, W, 3], got " + ", ".join(f"{a.dtype} {a.shape}" for a in pasted))
+    if any(a.shape != pasted[0].shape for a in pasted):
+        raise ValueError("generate_final_images: the turns' input images differ in size: " + ", ".join(str(a.shape[:2]) for a in pasted))
+    if any(tuple(m.size) != tuple(inp_masks[0].size) for m in inp_masks):
+        raise ValueError("generate_final_images: the turns' masks differ in size: " + ", ".join(str(tuple(m.size)) for m in inp_masks))
+    if any(not lst for lst in single_obj_img_lists):
+        raise ValueError("generate_final_images: every turn needs its first character image (single_obj_img_lists[i][0])")
+    texts = [emb[0] for emb in input_embeddings_list]
+    if any(tuple(t.shape) != tuple(texts[0].shape) for t in texts):
+        raise ValueError("generate_final_images: the turns' text embeddings differ in shape: " + ", ".join(str(tuple(t.shape)) for t in texts))
+    if any(tuple(la.shape) != tuple(latents_all_list[0].shape) for la in latents_all_list):
+        raise ValueError("generate_final_images: the turns' latents_all differ in shape: " + ", ".join(str(tuple(la.shape)) for la in latents_all_list))
+    unet = _own_unet(adapter, "generate_final_images")
+    from .controlnet import ControlNetModel
+    controlnet = controlnetpipe.controlnet
+    if not isinstance(controlnet, ControlNetModel):
+        raise TypeError("theatergen_amd.pipelines.generate_final_images: controlnetpipe.controlnet must be a theatergen_amd.controlnet.ControlNetModel "
+                        f"(INTEGRATION.md, stage 2), got {type(controlnet).__name__}")
+    vae, scheduler, dtype, dev = adapter.pipe.vae, adapter.pipe.scheduler, unet.dtype, unet.device
+    h8, w8 = int(height / 8), int(width / 8)
+    # ---- per turn, on the host: frozen mask, conditioning rows, control image (the single call's expressions and call order)
+    masks, rows, controls = [], [], []
+    for i in range(n):
+        m = np.array(inp_masks[i].resize((h8, w8)).convert("L")).astype(np.float32) / 255.0
+        m[m > 0] = 1
+        masks.append(torch.from_numpy(1 - m))
+        rows.append(_text_and_image_rows(adapter, overall_prompts[i], overall_negative_prompts[i], single_obj_img_lists[i][0]))          # [2, L, D]
+        controls.append(_control_image(controlnetpipe, processor(np.array(input_imgs[i])), width, height, dev, dtype))               # [2, 3, H, W]
+    if any(tuple(r.shape) != tuple(rows[0].shape) for r in rows):
+        raise ValueError("generate_final_images: the turns' conditioning rows differ in length: " + ", ".join(str(tuple(r.shape)) for r in rows))
+    if any(tuple(c.shape) != tuple(controls[0].shape) for c in controls):
+        raise ValueError("generate_final_images: the turns' control images differ in size: " + ", ".join(str(tuple(c.shape)) for c in controls))
+    adapter.set_scale(0.1)
+    scheduler.set_timesteps(num_inference_steps)
+    # ---- frozen latents: the n pasted images cross to the device as bytes, one encode, every turn's draws from its own device generator
+    u8 = torch.from_numpy(np.ascontiguousarray(np.stack(pasted))).to(dev)
+    dist = vae.encode(ops.image_from_u8(u8, dtype, range_mode=1)).latent_dist
+    gens = [torch.Generator(dev).manual_seed(s) for s in bg_seeds]
+    post_shape = (1, dist.parameters.shape[1] // 2) + tuple(dist.parameters.shape[2:])
+    post_noise = torch.cat([torch.randn(post_shape, generator=g, device=dev, dtype=dtype) for g in gens])
+    init_latents = vae.config.scaling_factor * dist.sample(noise=post_noise)                                                        # [n, C, h, w]
+    noise = torch.cat([torch.randn(post_shape, generator=g, device=dev, dtype=dtype) for g in gens])
+    my_latents = scheduler.add_noise(init_latents[None], noise[None], scheduler.timesteps)                                          # [steps, n, C, h, w]
+    my_bg = torch.cat([torch.randn((1, unet.config.in_channels, h8, w8), generator=g, device=dev, dtype=dtype) for g in gens]) * float(scheduler.init_noise_sigma)
+    for i, la in enumerate(latents_all_list):
+        la[0] = my_bg[i:i + 1].to(la.device, la.dtype)
+        la[1:] = my_latents[:, i:i + 1].to(la.device, la.dtype)
+    # ---- one engine, the turns in its batch dimension: negatives first, in turn order
+    enc = torch.cat([r[:1] for r in rows] + [r[1:] for r in rows], dim=0)
+    cn_enc = torch.cat([t[:1] for t in texts] + [t[1:] for t in texts], dim=0)
+    cn_cond = torch.cat([c[:1] for c in controls] + [c[1:] for c in controls], dim=0)
+    eng = _engine_of(adapter, n_img=n, height=int(cn_cond.shape[-2]), width=int(cn_cond.shape[-1]), num_inference_steps=num_inference_steps,
+                     guidance_scale=guidance_scale, enc_len=enc.shape[1], controlnet=controlnet, controlnet_enc_len=cn_enc.shape[1])
+    eng.set_conditioning(enc.to(dev, dtype))
+    eng.set_control(cn_enc.to(dev, dtype), cn_cond.to(dev, dtype), 1.0)
+    eng.set_frozen(torch.cat([la.to(dev, torch.float32) for la in latents_all_list], dim=1), torch.stack(masks).to(device=dev, dtype=torch.float32),
+                   frozen_steps)
+    latents = eng.run(my_bg)[-1].to(dtype)
+    images = ops.image_to_u8(vae.decode(1 / 0.18215 * latents).sample).cpu().numpy()                                                # [n, H, W, 3] bytes
+    return [(latents[i:i + 1], images[i:i + 1]) for i in range(n)]
+
+
+@torch.no_grad()
 def decode(vae, latents):
     """reference ``models/pipelines.py:163-173``: ``vae.decode(latents / 0.18215)`` -> ``(image / 2 + 0.5).clamp(0, 1)`` -> uint8 ``[n, H, W, 3]`` on the host"""
     image = vae.decode(1 / 0.18215 * latents).sample

@@ -226,9 +226,15 @@ class DiagonalGaussianDistribution:
     def logvar(self):
         return torch.clamp(self.parameters[:, self.parameters.shape[1] // 2:], -30.0, 20.0)
 
-    def sample(self, generator=None, scale=1.0):
+    def sample(self, generator=None, scale=1.0, noise=None):
+        """``noise`` (optional, [B, C, h, w]): the standard-normal draw to use instead of drawing here — a batch whose rows each come from their own
+        generator (``pipelines.generate_final_images``); ``generator`` is then not touched."""
         B, C2, h, w = self.parameters.shape
-        if generator is not None and generator.device.type != "cpu":
+        if noise is not None:
+            if tuple(noise.shape) != (B, C2 // 2, h, w):
+                raise ValueError(f"DiagonalGaussianDistribution.sample: noise shape {tuple(noise.shape)} != {(B, C2 // 2, h, w)}")
+            noise = noise.to(device=self.parameters.device, dtype=torch.float32).contiguous()
+        elif generator is not None and generator.device.type != "cpu":
             # a DEVICE generator (models/pipelines.py:594 `torch.Generator("cuda")`, stage 2): randn_tensor draws on the device in the model dtype
             noise = torch.randn((B, C2 // 2, h, w), generator=generator, device=self.parameters.device, dtype=self.dtype).to(torch.float32)
         else:

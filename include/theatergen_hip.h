@@ -283,6 +283,37 @@ int tg_attention_wide_splits(const tg_attn_desc* d, int32_t requested);
 int64_t tg_attention_wide_workspace_bytes(const tg_attn_desc* d, int32_t splits);
 int tg_attention_wide_split(const tg_attn_desc* d, int32_t splits, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Self-attention with SAM's DECOMPOSED RELATIVE-POSITION BIAS (csrc/tg_attention_relpos.hip; transformers' SamVisionAttention.get_decomposed_rel_pos),
+ * for the Segment-Anything image encoder that runs between the two stages (reference models/sam.py).  A batch item is one square grid of side `grid`:
+ * an image (grid 64) or one 14 x 14 window (grid 14); its N = grid^2 tokens are row-major, token i = (qh, qw) = (i / grid, i % grid).
+ *
+ * tg_relpos_tables: one launch per layer, all batch items and heads.  For kh, kw in [0, grid):
+ *     bh[b, h, i, kh] = sum_c q[b, i, h*d + c] * rel_pos_h[qh - kh + grid - 1, c]
+ *     bw[b, h, i, kw] = sum_c q[b, i, h*d + c] * rel_pos_w[qw - kw + grid - 1, c]
+ * q is the UNSCALED stored query (layout and pitches of tg_attn_desc: q[b, i, h*d + c], row pitch q_ld, batch pitch q_bs); rel_pos_h / rel_pos_w are dense
+ * [2 grid - 1, d] in the model dtype, shared by heads and batch items (a table of another length — transformers would interpolate it — is the caller's to
+ * refuse).  Products are exact in fp32 and summed in fp32 by one fma chain over c ascending: |error| <= 2^-20 * sum_c |q_c r_c| per element.  bh and bw are
+ * fp32, dense [batch, heads, N, grid], 16-byte aligned (ViT-H global layer: 2 x 16 x 4096 x 64 x 4 B = 33.5 MB per image).
+ *   TG_ERR_UNSUPPORTED  head_dim not in {64, 80}; grid not in {14, 64}.
+ *   TG_ERR_ARG          bad dtype, batch or heads < 1, a null pointer, q_ld (or q_bs with batch > 1) not a multiple of 8, misaligned pointers.
+ *
+ * tg_attention_relpos: with bh, bw as above,
+ *     O[b,h,i,:] = softmax_j( scale * q_i.k_j + bh[b,h,i, j / grid] + bw[b,h,i, j % grid] ) V
+ * Nothing [n_q, len0] exists in memory.  Scores q.k are accumulated in fp32 from the stored operands, scale and the bias are applied in fp32
+ * (x = fma(q.k, scale log2 e, (bh + bw) log2 e), p = exp2(x - running max)), P is rounded to the storage dtype where it enters the PV product and O
+ * is rounded once, as tg_attention does.  Layouts and pitches are tg_attention's (q | k token-major, V^T per batch item with vt0_ld >= len0 rounded up
+ * to 8).  At grid 14 every one of the 196 tokens of a window is a real key, the zero-padded positions included (their k, v are the projection bias).
+ * Instances: head_dim 64 and 80, bf16 and fp16, grid 64 and 14; three (d 64) / two (d 80) waves per SIMD, no scratch.  Everything else is refused on the host before any
+ * launch, writing nothing, with tg_last_error() set:
+ *   TG_ERR_UNSUPPORTED  another head_dim or grid; len1 != 0; causal, mask or w1_dev set.
+ *   TG_ERR_ARG          null descriptor / pointers (q, k0, vt0, out, bh, bw); n_q != grid^2 or len0 != grid^2; bad dtype; empty problem; scale <= 0;
+ *                       q_ld / k0_ld / vt0_ld not multiples of 8 or out_ld not a multiple of 4, with batch > 1 the same for the batch strides;
+ *                       q, k0, vt0, bh, bw not 16-byte aligned, out not 8-byte aligned.
+ * Additive to ABI 308: two new symbols, tg_attn_desc unchanged, TG_ABI_VERSION unchanged. */
+int tg_relpos_tables(int32_t dtype, int32_t batch, int32_t heads, int32_t head_dim, int32_t grid, const void* q, int64_t q_ld, int64_t q_bs,
+                     const void* rel_pos_h, const void* rel_pos_w, float* bh, float* bw, void* stream);
+int tg_attention_relpos(const tg_attn_desc* d, const float* bh, const float* bw, int32_t grid, void* stream);
+
 /* Reverse pass of SELF-attention without materialised probabilities (round 5, ABI 306; csrc/tg_attention_bwd.hip), head_dim <= 64, n % 8 == 0:
  *     dQ = dS K,  dK = dS^T Q,  dV = P^T dO   with  P = softmax(scale Q K^T),  dS = scale P o (dO V^T - rowsum(P o dO V^T))
  * — what `torch.autograd.grad(loss, latents)` of the guidance step (models/pipelines.py:62-128) computes through `Attention` / AttnProcessor

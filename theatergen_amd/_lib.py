@@ -143,6 +143,8 @@ SIGNATURES = {
     "tg_attention_wide_splits": (i32, [C.POINTER(AttnDesc), i32]),
     "tg_attention_wide_workspace_bytes": (i64, [C.POINTER(AttnDesc), i32]),
     "tg_attention_wide_split": (i32, [C.POINTER(AttnDesc), i32, vp, i64, vp]),
+    "tg_relpos_tables": (i32, [i32, i32, i32, i32, i32, vp, i64, i64, vp, vp, vp, vp, vp]),
+    "tg_attention_relpos": (i32, [C.POINTER(AttnDesc), vp, vp, i32, vp]),
     "tg_attention_bwd": (i32, [C.POINTER(AttnBwdDesc), vp]),
     "tg_attention_bwd_cross": (i32, [C.POINTER(AttnBwdCrossDesc), vp]),
     "tg_attention_bwd_wide": (i32, [C.POINTER(AttnBwdDesc), vp]),

@@ -133,6 +133,9 @@ HOT_GATES = [
     # the combine of the key-split partials (<T, D>): a streaming kernel, S loads per thread; scratch would mean its 4-float accumulator left the registers.
     # Ahead of the kernel gate only in the list: "attention_wide_kernel<" is not a substring of its name.  The SPLIT = true instances of the
     # main kernel (<T, D, DO, true>: fp32 partial epilogue) fall under the same 0-scratch / 256-VGPR gate as the unsplit ones
+    # SAM's rel-pos attention (tg_attention_relpos.hip, template <T, DPAD, DV, ONES, G>): two waves per SIMD; the bias lives in registers (32 Bw values at
+    # G = 64, 14 + 14 table entries at G = 14 with the tile loop unrolled) — scratch would mean one of those arrays was indexed at run time
+    ("attention_relpos_kernel<", 0, 256),
     ("attention_wide_combine_kernel<", 0, 64),
     ("attention_wide_kernel<", 0, 256),
     ("gemm_glds_kernel<", 0, 256),                                 # the LDS-DMA GEMM family: no scratch anywhere

@@ -533,6 +533,59 @@ def attention(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch,
     return out
 
 
+def relpos_table_floats(batch, heads, grid):
+    """fp32 elements of ONE of the two bias tables [batch, heads, grid^2, grid]."""
+    return int(batch) * int(heads) * int(grid) ** 3
+
+
+def relpos_tables(q, q_ld, q_bs, rel_pos_h, rel_pos_w, batch, heads, head_dim, grid, out=None):
+    """``tg_relpos_tables``: SAM's decomposed relative-position bias as two fp32 tables ``(bh, bw)``, each [batch, heads, grid^2, grid], from the
+    stored unscaled ``q`` (pitches as ``attention``) and the layer's ``rel_pos_h`` / ``rel_pos_w`` ([2 grid - 1, head_dim], the dtype of ``q``).
+    ``out``: a caller pair ``(bh, bw)``; default: both halves of ``ops.workspace`` (valid until the next kernel that takes scratch from it)."""
+    _need_cuda(q)
+    _need_cuda(rel_pos_h)
+    _need_cuda(rel_pos_w)
+    want = (2 * int(grid) - 1, int(head_dim))
+    for name, t in (("rel_pos_h", rel_pos_h), ("rel_pos_w", rel_pos_w)):
+        if tuple(t.shape) != want or t.dtype != q.dtype or not t.is_contiguous():
+            raise RuntimeError(f"relpos_tables: {name} must be a contiguous {q.dtype} tensor {want} (a table of another length would need "
+                               f"interpolation, which is not done here), got {tuple(t.shape)} {t.dtype}")
+    n = relpos_table_floats(batch, heads, grid)
+    if out is None:
+        n16 = (n + 3) // 4 * 4
+        ws = workspace(2 * n16 * 4, q.device)
+        bh, bw = ws[:n].view(batch, heads, grid * grid, grid), ws[n16:n16 + n].view(batch, heads, grid * grid, grid)
+    else:
+        bh, bw = out
+        for t in (bh, bw):
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != n:
+                raise RuntimeError(f"relpos_tables: out must be two contiguous fp32 device tensors of {n} elements")
+    _lib.check(_lib.lib().tg_relpos_tables(_dt(q), int(batch), int(heads), int(head_dim), int(grid), _ptr(q), int(q_ld), int(q_bs),
+                                           _ptr(rel_pos_h), _ptr(rel_pos_w), _ptr(bh), _ptr(bw), _stream()))
+    return bh, bw
+
+
+def attention_relpos(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, batch, heads, head_dim, grid, scale, bh, bw, out, out_ld, out_bs):
+    """``tg_attention_relpos``: one-segment flash self-attention over ``grid``^2 tokens with the separable score bias
+    ``bh[b, h, i, j // grid] + bw[b, h, i, j % grid]`` (``relpos_tables``) — the argument list of ``attention`` with n_q = len0 = grid^2."""
+    _need_cuda(q)
+    n = relpos_table_floats(batch, heads, grid)
+    for t in (bh, bw):
+        _need_cuda(t)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise RuntimeError(f"attention_relpos: bh / bw must be contiguous fp32 device tensors of {n} elements ([batch, heads, grid^2, grid])")
+    d = AttnDesc()
+    d.dtype = _dt(q)
+    d.batch, d.heads, d.head_dim, d.n_q, d.len0 = int(batch), int(heads), int(head_dim), int(grid) ** 2, int(grid) ** 2
+    d.q, d.q_ld, d.q_bs = _ptr(q), int(q_ld), int(q_bs)
+    d.k0, d.k0_ld, d.k0_bs = _ptr(k0), int(k0_ld), int(k0_bs)
+    d.vt0, d.vt0_ld, d.vt0_bs = _ptr(vt0), int(vt0_ld), int(vt0_bs)
+    d.scale = float(scale)
+    d.out, d.out_ld, d.out_bs = _ptr(out), int(out_ld), int(out_bs)
+    _lib.check(_lib.lib().tg_attention_relpos(C.byref(d), _ptr(bh), _ptr(bw), int(grid), _stream()))
+    return out
+
+
 def attention_wide(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale, out, out_ld, out_bs, key_splits=None):
     """``tg_attention_wide``: one-segment flash attention for head dims 256 / 512 (the VAE mid block), the argument list of ``attention`` without
     the second segment, mask, causal flag and device scalar.  Another head dim is an error (``attention`` takes multiples of 8 up to 160).

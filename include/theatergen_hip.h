@@ -840,6 +840,36 @@ int64_t tg_xq_kv_bytes(int32_t batch, int32_t C, int32_t head_dim);
 int tg_xq_kv_pack(int32_t dtype, int32_t batch, int32_t C, int32_t head_dim, const void* k, const void* vt, int64_t ldt, int32_t text_len, const void* kip,
                   const void* vtip, int64_t ldi, int32_t ip_tokens, void* out, void* stream);
 
+/* SAM's prompt encoder / mask decoder pieces that are not GEMMs, attention or LayerNorm (csrc/tg_sam_head.hip).  Additive to ABI 308: three new symbols,
+ * no descriptor, TG_ABI_VERSION unchanged.
+ *
+ * tg_sam_posenc: the random-Fourier positional encoding (transformers SamPositionalEmbedding).  `coords` fp32 [n, 2] = (x, y) already divided by the input
+ * size, `gauss` fp32 [2, F] (shared_image_embedding.positional_embedding); out [n, 2F] = [sin(2 pi t) | cos(2 pi t)], t = (2 c - 1) gauss, as out_dtype
+ * (TG_BF16, TG_F16 or 2 = fp32).  fp32 arithmetic, the argument reduced in turns (t - rint(t), exact) before the sine / cosine.  Optional `labels` int32 [n]
+ * with `table` fp32 [5, 2F] (rows 0..3 = point_embed[0..3], row 4 = not_a_point_embed), both or neither: label >= 0 adds row min(label, 3) in fp32 before
+ * the one rounding to out_dtype, label < 0 replaces the row by table row 4.  TG_ERR_ARG before any launch: bad dtype, n <= 0, F <= 0, a null coords /
+ * gauss / out, labels without table or the reverse. */
+int tg_sam_posenc(int32_t out_dtype, const float* coords, int64_t n, const float* gauss, int32_t F, const int32_t* labels, const float* table, void* out,
+                  void* stream);
+/* tg_sam_mask_head: the mask decoder's upscaling path and hypernetwork product in one launch.  `x` [images * g * g, 256] storage dtype, token-major (the
+ * image tokens after the two-way transformer); upscale_conv1 (ConvTranspose2d 256 -> 64, k = s = 2) -> LayerNorm over the 64 channels of every output
+ * pixel (eps) -> erf GELU -> upscale_conv2 (64 -> 32, k = s = 2) -> GELU -> out[p, m, y, x] = sum_c hyper_in[p, m, c] * upscaled[p, c, y, x], fp32
+ * [images, M, 4g, 4g]; token (i, j) makes the pixels (4 i + 2 a + a', 4 j + 2 b + b').  `w1` / `w2`: MFMA fragments of the two ConvTranspose weights,
+ * `vec` fp32 [224] = conv1 bias | LayerNorm weight | LayerNorm bias | conv2 bias (host: weights_pack.pack_sam_upscale); `hyper_in` [images, M, 32] storage
+ * dtype.  fp32 accumulation; the LayerNorm + GELU output is rounded once to the storage dtype (the second GEMM's operand), nothing else is.
+ * TG_ERR_UNSUPPORTED: g not a multiple of 8 or > 64, M > 4.  TG_ERR_ARG: bad dtype, images / g / M <= 0, eps <= 0, a null or misaligned pointer
+ * (x, w1, w2, vec 16 bytes; hyper_in, out 8). */
+int tg_sam_mask_head(int32_t dtype, const void* x, int32_t images, int32_t g, const void* w1, const void* w2, const float* vec, const void* hyper_in,
+                     int32_t M, float eps, float* out, void* stream);
+/* tg_sam_mask_post: transformers' post_process_masks followed by the reference's resize to the target shape (models/sam.py:50), per plane of fp32
+ * `logits` [planes, L, L]:  bilinear L -> S (align_corners = false: src = max(scale (dst + 0.5) - 0.5, 0), i1 = min(i0 + 1, in - 1)), crop [:hr, :wr],
+ * bilinear to (h0, w0), > threshold, then F.interpolate(mask.float(), (ht, wt), 'bilinear').bool() = the OR of the original-size mask over the taps of
+ * non-zero weight.  `mask` uint8 [planes, ht, wt] (0 / 1), `areas` int32 [planes] = the sum of each plane of `mask` (cleared on the stream, then integer
+ * atomics: deterministic).  No S x S tensor: every output pixel evaluates its taps from the logits.
+ * TG_ERR_ARG before any launch: a size <= 0, hr or wr > S, a side > 32768, planes > 65535, a null pointer. */
+int tg_sam_mask_post(const float* logits, int32_t planes, int32_t L, int32_t S, int32_t hr, int32_t wr, int32_t h0, int32_t w0, float threshold,
+                     int32_t ht, int32_t wt, uint8_t* mask, int32_t* areas, void* stream);
+
 /* debugging aid: raw 32x32x16 MFMA on caller-provided fragments (64 lanes x 8 elements each) */
 int tg_debug_mfma32(int32_t dtype, const void* a_frags, const void* b_frags, float* d_out, void* stream);
 

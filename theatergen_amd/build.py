@@ -136,6 +136,12 @@ HOT_GATES = [
     # SAM's rel-pos attention (tg_attention_relpos.hip, template <T, DPAD, DV, ONES, G>): two waves per SIMD; the bias lives in registers (32 Bw values at
     # G = 64, 14 + 14 table entries at G = 14 with the tile loop unrolled) — scratch would mean one of those arrays was indexed at run time
     ("attention_relpos_kernel<", 0, 256),
+    # SAM's prompt / mask head (tg_sam_head.hip).  The mask head keeps two GEMMs' accumulators, the LayerNorm and the second GEMM's B operand in registers
+    # with compile-time indices (scratch = one of those arrays was indexed at run time); the positional encoding calls the precise sinf / cosf on a reduced
+    # argument (scratch = the large-argument path's tables came back); the post-processing is scalar code
+    ("sam_mask_head_kernel<", 0, 128),
+    ("sam_posenc_kernel<", 0, 64),
+    ("sam_mask_post_kernel", 0, 96),
     ("attention_wide_combine_kernel<", 0, 64),
     ("attention_wide_kernel<", 0, 256),
     ("gemm_glds_kernel<", 0, 256),                                 # the LDS-DMA GEMM family: no scratch anywhere

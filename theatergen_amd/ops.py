@@ -586,6 +586,90 @@ def attention_relpos(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, batch
     return out
 
 
+def _f32_dev(t, what, numel=None):
+    _need_cuda(t)
+    if t.dtype != torch.float32 or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        raise RuntimeError(f"{what} must be a contiguous fp32 device tensor" + (f" of {numel} elements" if numel is not None else "") +
+                           f", got {tuple(t.shape)} {t.dtype}")
+
+
+def sam_posenc(coords, gauss, labels=None, table=None, dtype=torch.float32, out=None):
+    """``tg_sam_posenc``: coords fp32 [n, 2] (x, y in units of the input size), gauss fp32 [2, F] -> [n, 2F] = [sin | cos](2 pi (2 c - 1) gauss) as ``dtype``
+    (fp32, bf16 or fp16), all arithmetic in fp32.  ``labels`` int32 [n] + ``table`` fp32 [5, 2F] (point_embed[0..3], not_a_point_embed): label >= 0 adds its
+    row, label -1 replaces the encoding by row 4."""
+    _f32_dev(coords, "sam_posenc: coords")
+    _f32_dev(gauss, "sam_posenc: gauss")
+    if coords.ndim != 2 or coords.shape[1] != 2 or gauss.ndim != 2 or gauss.shape[0] != 2:
+        raise RuntimeError(f"sam_posenc: coords [n, 2] and gauss [2, F] expected, got {tuple(coords.shape)} and {tuple(gauss.shape)}")
+    n, F_ = int(coords.shape[0]), int(gauss.shape[1])
+    if (labels is None) != (table is None):
+        raise RuntimeError("sam_posenc: labels and table come together")
+    if labels is not None:
+        _need_cuda(labels)
+        if labels.dtype != torch.int32 or not labels.is_contiguous() or labels.numel() != n:
+            raise RuntimeError(f"sam_posenc: labels must be a contiguous int32 device tensor of {n} elements")
+        _f32_dev(table, "sam_posenc: table", 5 * 2 * F_)
+    code = 2 if dtype == torch.float32 else _lib.TG_BF16 if dtype == torch.bfloat16 else _lib.TG_F16 if dtype == torch.float16 else None
+    if code is None:
+        raise RuntimeError(f"sam_posenc: output dtype {dtype} unsupported (fp32, bf16, fp16)")
+    if out is None:
+        out = torch.empty((n, 2 * F_), dtype=dtype, device=coords.device)
+    elif out.dtype != dtype or not out.is_cuda or not out.is_contiguous() or out.numel() != n * 2 * F_:
+        raise RuntimeError(f"sam_posenc: out must be a contiguous {dtype} device tensor [{n}, {2 * F_}]")
+    _lib.check(_lib.lib().tg_sam_posenc(code, _ptr(coords), n, _ptr(gauss), F_, _ptr(labels), _ptr(table), _ptr(out), _stream()))
+    return out
+
+
+def sam_mask_head(x, images, g, w1, w2, vec, hyper_in, eps=1e-6, out=None):
+    """``tg_sam_mask_head``: image tokens x [images * g * g, 256] -> fp32 low-resolution logits [images, M, 4g, 4g] (upscale_conv1, LayerNorm, GELU,
+    upscale_conv2, GELU, product with ``hyper_in`` [images, M, 32]) in one launch.  ``w1, w2, vec = weights_pack.pack_sam_upscale(...)``."""
+    _need_cuda(x)
+    for t in (w1, w2, hyper_in):
+        _need_cuda(t)
+        if t.dtype != x.dtype or not t.is_contiguous():
+            raise RuntimeError(f"sam_mask_head: w1, w2 and hyper_in must be contiguous {x.dtype} device tensors")
+    images, g = int(images), int(g)
+    if x.ndim != 2 or tuple(x.shape) != (images * g * g, 256) or not x.is_contiguous():
+        raise RuntimeError(f"sam_mask_head: x must be contiguous [{images * g * g}, 256], got {tuple(x.shape)}")
+    if hyper_in.ndim != 3 or hyper_in.shape[0] != images or hyper_in.shape[2] != 32:
+        raise RuntimeError(f"sam_mask_head: hyper_in must be [{images}, M, 32], got {tuple(hyper_in.shape)}")
+    if w1.numel() != 4 * 64 * 256 or w2.numel() != 4 * 32 * 64:
+        raise RuntimeError("sam_mask_head: w1 / w2 are not weights_pack.pack_sam_upscale's fragments")
+    _f32_dev(vec, "sam_mask_head: vec", 224)
+    M = int(hyper_in.shape[1])
+    if out is None:
+        out = torch.empty((images, M, 4 * g, 4 * g), dtype=torch.float32, device=x.device)
+    else:
+        _f32_dev(out, "sam_mask_head: out", images * M * 16 * g * g)
+    _lib.check(_lib.lib().tg_sam_mask_head(_dt(x), _ptr(x), images, g, _ptr(w1), _ptr(w2), _ptr(vec), _ptr(hyper_in), M, float(eps), _ptr(out), _stream()))
+    return out
+
+
+def sam_mask_post(logits, padded_size, reshaped_size, original_size, target_size, threshold=0.0, out=None):
+    """``tg_sam_mask_post``: fp32 logits [..., L, L] -> (uint8 mask [..., ht, wt], int32 areas [...]): post_process_masks (bilinear to ``padded_size``, crop to
+    ``reshaped_size`` (hr, wr), bilinear to ``original_size`` (h0, w0), > threshold) and the reference's bilinear resize of the boolean mask to
+    ``target_size`` (ht, wt), fused.  ``out``: a caller pair (mask, areas)."""
+    _f32_dev(logits, "sam_mask_post: logits")
+    if logits.ndim < 3 or logits.shape[-1] != logits.shape[-2]:
+        raise RuntimeError(f"sam_mask_post: logits [..., L, L] expected, got {tuple(logits.shape)}")
+    lead, L = tuple(logits.shape[:-2]), int(logits.shape[-1])
+    planes = 1
+    for s in lead:
+        planes *= int(s)
+    (hr, wr), (h0, w0), (ht, wt) = [tuple(int(v) for v in s) for s in (reshaped_size, original_size, target_size)]
+    if out is None:
+        mask = torch.empty(lead + (max(ht, 0), max(wt, 0)), dtype=torch.uint8, device=logits.device)
+        areas = torch.empty(lead, dtype=torch.int32, device=logits.device)
+    else:
+        mask, areas = out
+        if (mask.dtype != torch.uint8 or areas.dtype != torch.int32 or not mask.is_cuda or not areas.is_cuda or not mask.is_contiguous()
+                or not areas.is_contiguous() or mask.numel() != planes * ht * wt or areas.numel() != planes):
+            raise RuntimeError(f"sam_mask_post: out must be (uint8 [{planes}, {ht}, {wt}], int32 [{planes}]) contiguous device tensors")
+    _lib.check(_lib.lib().tg_sam_mask_post(_ptr(logits), planes, L, int(padded_size), hr, wr, h0, w0, float(threshold), ht, wt, _ptr(mask), _ptr(areas),
+                                           _stream()))
+    return mask, areas
+
+
 def attention_wide(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale, out, out_ld, out_bs, key_splits=None):
     """``tg_attention_wide``: one-segment flash attention for head dims 256 / 512 (the VAE mid block), the argument list of ``attention`` without
     the second segment, mask, causal flag and device scalar.  Another head dim is an error (``attention`` takes multiples of 8 up to 160).

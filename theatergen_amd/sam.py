@@ -4,7 +4,9 @@
 The encoder (``transformers.SamVisionEncoder``: a ViT at 1024 x 1024, 4096 tokens; ViT-H 32 layers x 1280 channels x 16 heads of 80) is >99 % of
 the model and the reference runs it TWICE per character (``sam_refine_attn`` calls ``sam_box_input`` once per target mask shape).  Here
 ``sam_refine_attn`` computes the embeddings once and serves both shapes; the prompt encoder and mask decoder stay the caller's transformers modules
-(``SamModel(image_embeddings=..., input_boxes=...)``).
+(``SamModel(image_embeddings=..., input_boxes=...)``) — unless ``sam_model`` is ``theatergen_amd.sam_decoder.SamModel``: then prompt encoder, mask decoder and
+the mask post-processing run on the device as well (``_sam_device``: one processor call, one encoder run, one decoder run, one copy back), for one character
+(``sam``, ``sam_refine_attn``) or a list of them (``sam_refine_characters``).
 
 Token-major throughout, as ``clip.py``: patch embedding = one GEMM over the unfolded 16 x 16 patches with ``pos_embed`` as the residual operand;
 per layer LayerNorm, one Q|K|V^T projection GEMM, ``relpos_tables`` + ``attention_relpos`` (the decomposed relative-position bias added tile by tile,
@@ -250,12 +252,83 @@ def sam_image_embeddings(sam_model_dict, image):
         return enc(inputs["pixel_values"].to(enc.device))
 
 
+def _on_device_route(sam_model):
+    from .sam_decoder import SamModel
+    return isinstance(sam_model, SamModel)
+
+
+def _prompt_array(x, last, what):
+    """nested lists / tuples / arrays / CPU tensors -> float64 [B, nb, ..., last]: one image's prompts may come without the image axis"""
+    a = np.asarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=np.float64)
+    if a.ndim == 0 or a.shape[-1] != last:
+        raise ValueError(f"{what}: last dimension {last} expected, got shape {a.shape}")
+    want = 3 if last == 4 else 4
+    while a.ndim < want:
+        a = a[None]
+    if a.ndim != want:
+        raise ValueError(f"{what}: shape {a.shape} has too many dimensions")
+    return a
+
+
+def _sam_device(sam_model_dict, images, input_points, input_boxes, target_shapes, image_embeddings=None):
+    """The device route behind ``sam`` / ``sam_refine_attn`` / ``sam_refine_characters``: ONE processor call (image resize + normalisation; prompts are
+    rescaled here, as the processor does: x * new_w / old_w, y * new_h / old_h in float64), one encoder run unless ``image_embeddings`` come along, one
+    decoder run, one ``ops.sam_mask_post`` launch per image and target shape, ONE copy back.
+    -> (masks[t][b] bool [nb, m, h_t, w_t] (torch, host), areas[t][b] int64 [nb, m], iou fp32 numpy [B, nb, m])"""
+    model, proc = sam_model_dict["sam_model"], sam_model_dict["sam_processor"]
+    with torch.no_grad():
+        inputs = proc(images, return_tensors="pt")
+        pv = inputs["pixel_values"]
+        orig = np.asarray(inputs["original_sizes"]).reshape(-1, 2).astype(np.int64)
+        resh = np.asarray(inputs["reshaped_input_sizes"]).reshape(-1, 2).astype(np.int64)
+        B, S = int(pv.shape[0]), int(pv.shape[-1])
+        ratio = np.stack([resh[:, 1] / orig[:, 1], resh[:, 0] / orig[:, 0]], -1)                      # [B, (x, y)]
+        kw = {}
+        if input_boxes is not None:
+            bx = _prompt_array(input_boxes, 4, "input_boxes")
+            kw["input_boxes"] = (bx.reshape(bx.shape[0], -1, 2, 2) * ratio[:, None, None, :]).reshape(bx.shape)
+        if input_points is not None:
+            pts = _prompt_array(input_points, 2, "input_points")
+            kw["input_points"] = pts * ratio[:, None, None, :]
+            kw["input_labels"] = np.ones(pts.shape[:3], np.int32)
+        for k, v in kw.items():
+            if v.shape[0] != B:
+                raise ValueError(f"{k}: prompts for {v.shape[0]} images, {B} images")
+        if image_embeddings is None:
+            enc = sam_model_dict.get("sam_encoder") or model.vision_encoder
+            image_embeddings = enc(pv.to(model.device))
+        out = model(image_embeddings=image_embeddings, **kw)
+        dev_masks, dev_areas = [], []
+        for shape in target_shapes:
+            for b in range(B):
+                m, a = ops.sam_mask_post(out.pred_masks[b], S, resh[b], orig[b], shape)
+                dev_masks.append(m)
+                dev_areas.append(a)
+        # one copy back: every result as bytes of one buffer, widest elements first (the host views stay aligned)
+        parts = dev_areas + [out.iou_scores] + dev_masks
+        flat = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu()
+    host, o = [], 0
+    for t in parts:
+        nbytes = t.numel() * t.element_size()
+        host.append(flat[o:o + nbytes].clone().view(t.dtype).reshape(t.shape))
+        o += nbytes
+    n = len(dev_areas)
+    areas, iou, masks = host[:n], host[n].float().numpy(), host[n + 1:]
+    T = len(target_shapes)
+    return ([[masks[t * B + b].bool() for b in range(B)] for t in range(T)], [[areas[t * B + b].long() for b in range(B)] for t in range(T)], iou)
+
+
 def sam(sam_model_dict, image, input_points=None, input_boxes=None, target_mask_shape=None, return_numpy=True, image_embeddings=None):
     """Reference ``models/sam.py:26-56`` with the image encoder replaced: ``sam_model_dict['sam_encoder']`` (``SamVisionEncoder`` above) makes the image
     embeddings unless ``image_embeddings`` brings them; ``sam_model`` (the caller's ``transformers.SamModel``) runs its prompt encoder and mask decoder
-    on them.  The encoder's own dtype replaces the reference's ``torch.autocast`` for the encoder part.  target_mask_shape: (h, w)."""
+    on them.  The encoder's own dtype replaces the reference's ``torch.autocast`` for the encoder part.  target_mask_shape: (h, w).
+    With ``sam_model`` a ``theatergen_amd.sam_decoder.SamModel`` the whole step stays on the device (``_sam_device``): the same return structure, the masks
+    thresholded and resized by ``ops.sam_mask_post``."""
     import torch.nn.functional as F
     sam_model, proc = sam_model_dict["sam_model"], sam_model_dict["sam_processor"]
+    if _on_device_route(sam_model):
+        masks, _, iou = _sam_device(sam_model_dict, image, input_points, input_boxes, [tuple(target_mask_shape)], image_embeddings)
+        return [m.numpy() if return_numpy else m for m in masks[0]], iou[0, 0]
     input_boxes = _listify_boxes(input_boxes)
     with torch.no_grad():
         inputs = proc(image, input_points=input_points, input_boxes=input_boxes, return_tensors="pt")
@@ -290,7 +363,13 @@ def select_mask(masks, conf_scores, coarse_ious=None, rule="largest_over_conf", 
     confidence or coarse IoU is below its threshold is set back by the size of the largest one.  -> (mask, its confidence)."""
     masks = np.asarray(masks)
     conf_scores = np.asarray(conf_scores)
-    mask_sizes = masks.sum(axis=(1, 2))
+    mask_id = _select_mask_id(masks.sum(axis=(1, 2)), conf_scores, coarse_ious, rule, discourage_mask_below_confidence,
+                              discourage_mask_below_coarse_iou, verbose)
+    return masks[mask_id], conf_scores[mask_id]
+
+
+def _select_mask_id(mask_sizes, conf_scores, coarse_ious, rule, discourage_mask_below_confidence, discourage_mask_below_coarse_iou, verbose):
+    """``select_mask``'s rule on the mask sizes alone (the device route brings them from ``ops.sam_mask_post``)"""
     if rule != "largest_over_conf":
         raise ValueError(f"Unknown rule: {rule}")
     max_mask_size = np.max(mask_sizes)
@@ -301,7 +380,32 @@ def select_mask(masks, conf_scores, coarse_ious=None, rule="largest_over_conf", 
     if verbose:
         print(f"mask_sizes: {mask_sizes}, scores: {scores}")
         print(f"Selected a mask with confidence: {conf_scores[mask_id]}, coarse_iou: {coarse_ious[mask_id] if coarse_ious is not None else None}")
-    return masks[mask_id], conf_scores[mask_id]
+    return mask_id
+
+
+def sam_refine_characters(images, input_boxes, model_dict, height, width, discourage_mask_below_confidence, discourage_mask_below_coarse_iou,
+                          verbose=False):
+    """``sam_refine_attn`` (box prompts) for a list of characters at once — the companion of ``generate_characters``: one processor call, one encoder run and
+    one decoder run at batch n, two ``ops.sam_mask_post`` launches per character, one copy back.  ``images[i]`` / ``input_boxes[i]``: what ``sam_refine_attn``
+    takes as ``sam_input_image`` / ``input_boxes_w`` for character i (every character with the same number of boxes).  Needs the device route
+    (``model_dict['sam_model']`` a ``theatergen_amd.sam_decoder.SamModel``).  -> four lists (mask, conf, mask_512, conf_512), entry i = ``sam_refine_attn`` of i."""
+    if not _on_device_route(model_dict["sam_model"]):
+        raise NotImplementedError("sam_refine_characters needs model_dict['sam_model'] to be a theatergen_amd.sam_decoder.SamModel (the device route)")
+    images = list(images)
+    boxes = np.concatenate([_prompt_array(b, 4, "input_boxes") for b in input_boxes], 0)
+    if boxes.shape[0] != len(images):
+        raise ValueError(f"sam_refine_characters: {len(images)} images, boxes for {boxes.shape[0]}")
+    shapes = [(int(height / 8), int(width / 8)), (int(height), int(width))]
+    masks, areas, iou = _sam_device(model_dict, images, None, boxes, shapes)
+    out = ([], [], [], [])
+    for b in range(len(images)):
+        conf = iou[b, 0]
+        for t in range(2):
+            mid = _select_mask_id(areas[t][b][0].numpy(), conf, None, "largest_over_conf", discourage_mask_below_confidence,
+                                  discourage_mask_below_coarse_iou, bool(verbose))
+            out[2 * t].append(masks[t][b][0, mid].numpy())
+            out[2 * t + 1].append(conf[mid])
+    return out
 
 
 def sam_refine_attn(input_boxes_w, obj_id, sam_input_image, token_attn_np, model_dict, height, width, H, W, use_box_input, gaussian_sigma,
@@ -312,6 +416,11 @@ def sam_refine_attn(input_boxes_w, obj_id, sam_input_image, token_attn_np, model
     if use_box_input:
         raise NotImplementedError("sam_refine_attn: use_box_input=True cannot run in the reference either (its token_attn_np_smooth is the int 1, "
                                   "models/sam.py:134-141); only the box-prompt path (use_box_input=False) is supported")
+    if _on_device_route(model_dict["sam_model"]):
+        # one processor call, one encoder run, one decoder run, two post-processing launches, one host synchronisation
+        r = sam_refine_characters([sam_input_image], [input_boxes_w], model_dict, height, width, discourage_mask_below_confidence,
+                                  discourage_mask_below_coarse_iou, verbose)
+        return r[0][0], r[1][0], r[2][0], r[3][0]
     H, W = int(height / 8), int(width / 8)
     emb = sam_image_embeddings(model_dict, sam_input_image)
     masks, conf_scores = sam_box_input(model_dict, image=sam_input_image, input_boxes=input_boxes_w, target_mask_shape=(H, W), image_embeddings=emb)

@@ -126,6 +126,40 @@ def rc_pack_tiles(w: torch.Tensor, v: torch.Tensor = None, u: torch.Tensor = Non
     return torch.cat([out, torch.zeros(3 * 1024, dtype=torch.uint8, device=w.device)])
 
 
+def convtranspose2x2_matrices(w: torch.Tensor) -> torch.Tensor:
+    """ConvTranspose2d weight [Cin, Cout, 2, 2] with stride 2 -> [4, Cout, Cin]: matrix 2 a + b makes output pixel (2 i + a, 2 j + b) from input pixel
+    (i, j) alone (kernel = stride: no two input pixels meet in one output pixel)."""
+    cin, cout, kh, kw = w.shape
+    assert kh == 2 and kw == 2
+    return w.detach().permute(2, 3, 1, 0).reshape(4, cout, cin).contiguous()
+
+
+def sam_upscale_k_order() -> torch.Tensor:
+    """[4, 2, 8] long: the input channel of element j of lane half hi in k-step ks of tg_sam_mask_head's second GEMM = the accumulator order of its first
+    (register 8 (ks & 1) + j of 32-channel tile ks >> 1): 16 ks + 8 (j >> 2) + 4 hi + (j & 3)."""
+    ks = torch.arange(4)[:, None, None]
+    hi = torch.arange(2)[None, :, None]
+    j = torch.arange(8)[None, None, :]
+    return 16 * ks + 8 * (j >> 2) + 4 * hi + (j & 3)
+
+
+def pack_sam_upscale(conv1_w, conv1_b, ln_w, ln_b, conv2_w, conv2_b):
+    """SAM mask decoder's ``upscale_conv1`` [256, 64, 2, 2], ``upscale_layer_norm`` [64] and ``upscale_conv2`` [64, 32, 2, 2] -> what tg_sam_mask_head reads:
+      w1  [4 (a, b), 2 tiles, 16 k-steps, 64 lanes, 8]: lane (hi, l31), element j = M1[ab][32 tile + l31, 16 ks + 8 hi + j]   (A operand of a 32x32x16 MFMA)
+      w2  [4 (a', b'), 4 k-steps, 64 lanes, 8]:          lane (hi, l31), element j = M2[a'b'][l31, sam_upscale_k_order()[ks, hi, j]]
+      vec fp32 [224] = conv1 bias | LayerNorm weight | LayerNorm bias | conv2 bias
+    with M = ``convtranspose2x2_matrices``; w1 / w2 keep the weights' dtype."""
+    assert tuple(conv1_w.shape) == (256, 64, 2, 2) and tuple(conv2_w.shape) == (64, 32, 2, 2), (conv1_w.shape, conv2_w.shape)
+    m1 = convtranspose2x2_matrices(conv1_w)                                                       # [4, 64, 256]
+    w1 = m1.reshape(4, 2, 32, 16, 2, 8).permute(0, 1, 3, 4, 2, 5).contiguous().reshape(-1)       # [ab, tile, ks, hi, l31, j]
+    m2 = convtranspose2x2_matrices(conv2_w)                                                       # [4, 32, 64]
+    kap = sam_upscale_k_order().to(m2.device)
+    w2 = m2[:, :, kap].permute(0, 2, 3, 1, 4).contiguous().reshape(-1)                           # [a'b', l31, ks, hi, j] -> [a'b', ks, hi, l31, j]
+    vec = torch.cat([t.detach().float().reshape(-1) for t in (conv1_b, ln_w, ln_b, conv2_b)]).contiguous()
+    assert vec.numel() == 224
+    return w1, w2, vec
+
+
 def skinny_pack(w: torch.Tensor) -> torch.Tensor:
     """Linear weight [N, K] (N % 32 == 0, K % 16 == 0) -> tg_skinny_gemm's fragment order: block (nt, ks) = 64 lanes x 8 elements, lane (hi, l31), element j =
     W[32 nt + l31, 16 ks + 8 hi + j] — the A operand of one 32x32x16 MFMA as ONE contiguous KiB, so the weight stream is whole-line loads in K order."""

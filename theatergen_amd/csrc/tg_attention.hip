@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
   float m_run = -INFINITY, l_run = 0.f;
 
   // ---- LDS-DMA tile loader
-  const int lrow = lane >> 3, slot = lane & 7;
+  const int lrow_lane = lane >> 3, slot_lane = lane & 7;
   const T* zero = reinterpret_cast<const T*>(attn_zero_page);
   auto dma = [&](const T* src, T* lds_row_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
@@ -140,6 +140,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
   auto issue = [&](const T* kb, long k_ld, const T* vb, long vt_ld, int len, int kv0, int stage) {
     T* sK = sbase + stage * STAGE;
     T* sV = sK + K_ELEMS;
+    // the lane's row and slot through an empty asm: the compiler must derive this call's addresses here, where they are used.  Otherwise it
+    // hoists the tile-invariant part of every request of every call site out of the tile loop and holds it in registers across the loop
+    // (2 per request, for a path that only ragged tiles and segment 1 take now; no instruction is emitted for the asm)
+    int lrow = lrow_lane, slot = slot_lane;
+    asm volatile("" : "+v"(lrow), "+v"(slot));
 #pragma unroll
     for (int j = 0; j < KJ; ++j) {
       const int q = j * 4 + wave;                       // rows [8q, 8q+8) of the panel stack
@@ -160,6 +165,61 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
       if (ONES && d == DV - 1) src = ones_page<T>();
       dma(src, sV + q * 512);
     }
+  };
+  // FULL tiles of segment 0 (kv0 + KV <= len0, not causal): nothing of a request's source address changes from tile to tile except a
+  // uniform stride (KV rows of K, KV columns of V^T), and which lanes read a constant page (head-dim padding, the FOLD / ONES pages) is fixed
+  // for the kernel.  So each request keeps a RUNNING source pointer: a full tile issues straight from it and advances it — no 64-bit
+  // multiply, no key-range compare, no page select in the tile loop (the loop is VALU-bound; `issue` costs 11 VALU instructions a request).
+  // Page lanes stay put: a K request's page lanes depend on the lane (d0 >= HD; the same lanes for both requests of a panel), so the K
+  // stride is a per-lane byte count, one register pair per panel, 0 on page lanes; a V^T request is all tensor or all page (HD is a multiple
+  // of 8, the request's rows start at a multiple of 8), so its stride is a scalar.  Ragged tiles, causal launches and segment 1 go
+  // through `issue`; the pointers advance once per staged tile, so they are those of the tile to stage whenever that tile is full.
+  const T* kb0 = reinterpret_cast<const T*>(p.k0) + (long)b * p.k0_bs + (long)h * HD;
+  const T* vb0 = reinterpret_cast<const T*>(p.vt0) + (long)b * p.vt0_bs + (long)h * HD * p.vt0_ld;
+  const bool fast = p.causal == 0;
+  const T* kp[KJ];
+  const T* vp[VJ];
+  unsigned long kstep[NP], vstep[VJ];
+#pragma unroll
+  for (int j = 0; j < KJ; ++j) {
+    const int q = j * 4 + wave;
+    const int prow = 8 * q + lrow_lane;
+    const int r = prow & 63, panel = prow >> 6;
+    const int d0 = panel * 64 + ((slot_lane ^ ((r >> 1) & 7)) << 3);
+    kp[j] = d0 < HD ? kb0 + (long)r * p.k0_ld + d0 : ((FOLD && d0 == HD) ? one0_page<T>() : zero);
+    if ((j & 1) == 0) kstep[j >> 1] = d0 < HD ? (unsigned long)p.k0_ld * (KV * sizeof(T)) : 0ul;      // panel = j >> 1
+  }
+#pragma unroll
+  for (int j = 0; j < VJ; ++j) {
+    const int q = j * 4 + wave;
+    const int d = 8 * q + lrow_lane;
+    vp[j] = d < HD ? vb0 + (long)d * p.vt0_ld + ((slot_lane ^ ((d >> 1) & 7)) << 3) : ((ONES && d == DV - 1) ? ones_page<T>() : zero);
+    vstep[j] = 8 * q < HD ? KV * sizeof(T) : 0ul;
+  }
+  // the advance as one tied instruction, pointer += bytes in place (`bytes`: a lane value for K, a scalar for V^T).  Written as `ptr + bytes` the
+  // allocator keeps the old and the new pointer in different registers and pays a 64-bit move per request and tile
+  auto bump_v = [](const T*& ptr, unsigned long bytes) { asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(ptr) : "v"(bytes)); };
+  auto bump_s = [](const T*& ptr, unsigned long bytes) { asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(ptr) : "s"(bytes)); };
+  auto issue_full = [&](int stage) {
+    T* sK = sbase + stage * STAGE;
+    T* sV = sK + K_ELEMS;
+#pragma unroll
+    for (int j = 0; j < KJ; ++j) dma(kp[j], sK + (j * 4 + wave) * 512);
+#pragma unroll
+    for (int j = 0; j < VJ; ++j) dma(vp[j], sV + (j * 4 + wave) * 512);
+  };
+  // on to the next tile.  Once per staged tile of segment 0, full or not and outside any branch (a branch around it is what makes the allocator
+  // split the pointers' registers); pointers that have run past the last full tile are not used again
+  auto advance = [&]() {
+#pragma unroll
+    for (int j = 0; j < KJ; ++j) bump_v(kp[j], kstep[j >> 1]);
+#pragma unroll
+    for (int j = 0; j < VJ; ++j) bump_s(vp[j], vstep[j]);
+  };
+  // segment 0's tile at keys kv0 .. kv0 + KV into `stage`
+  auto issue0 = [&](int kv0, int stage) {
+    if (fast && kv0 + KV <= p.len0) issue_full(stage);
+    else issue(kb0, p.k0_ld, vb0, p.vt0_ld, p.len0, kv0, stage);
   };
   // a 16-byte V^T chunk that straddles `len` brought columns >= len along (they may hold anything, and 0 * NaN = NaN
   // in the PV MFMA): zero them in LDS.  Only ragged tiles (text 77 = 64 + 13 keys, 4 image tokens) take this path.
@@ -246,14 +306,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
     }
   };
 
-  const T* kb0 = reinterpret_cast<const T*>(p.k0) + (long)b * p.k0_bs + (long)h * HD;
-  const T* vb0 = reinterpret_cast<const T*>(p.vt0) + (long)b * p.vt0_bs + (long)h * HD * p.vt0_ld;
-  const T* kb1 = reinterpret_cast<const T*>(p.k1) + (long)b * p.k1_bs + (long)h * HD;
+  const T* kb1 =reinterpret_cast<const T*>(p.k1) + (long)b * p.k1_bs + (long)h * HD;
   const T* vb1 = reinterpret_cast<const T*>(p.vt1) + (long)b * p.vt1_bs + (long)h * HD * p.vt1_ld;
 
   // ---------------- segment 0: online softmax over len0 keys
   const int nt0 = (p.len0 + KV - 1) / KV;
-  issue(kb0, p.k0_ld, vb0, p.vt0_ld, p.len0, 0, 0);
+  issue0(0, 0);
+  advance();
   for (int t = 0; t < nt0; ++t) {
     const int st = t & 1, kv0 = t * KV;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -262,8 +321,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
       fixup_v(p.len0 - kv0, st);
       __syncthreads();
     }
-    if (t + 1 < nt0) issue(kb0, p.k0_ld, vb0, p.vt0_ld, p.len0, kv0 + KV, st ^ 1);
+    if (t + 1 < nt0) issue0(kv0 + KV, st ^ 1);
     else if (p.len1 > 0) issue(kb1, p.k1_ld, vb1, p.vt1_ld, p.len1, 0, st ^ 1);
+    advance();
     const T* sK = sbase + st * STAGE;
     f32x16 s[2];
     scores(s, sK, p.len0, kv0, p.causal != 0);

@@ -286,11 +286,11 @@ def main():
             encoder_part(args.rounds, res)
     errors = json.load(open(args.errors)) if args.errors and os.path.exists(args.errors) else []
     res["errors_vs_fp64"] = errors
-    for path, text in ((args.out, json.dumps(res, indent=1)), (args.md, markdown(res, errors))):
+    for path, text in ((args.out, lambda: json.dumps(res, indent=1)), (args.md, lambda: markdown(res, errors))):       # --md needs the encoder part
         if path:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             with open(path, "w") as f:
-                f.write(text)
+                f.write(text())
 
 
 if __name__ == "__main__":

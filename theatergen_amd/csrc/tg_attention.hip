@@ -9,33 +9,23 @@
 // (w1 / l1) * exp(s1 - m1), so decoupled cross-attention costs one extra tile, not a second kernel.
 //
 // Work split: block = 4 waves x 32 queries; K tile [64 keys][d] and V^T tile [d][64 keys] in LDS, shared by
-// the 4 waves.  Everything is computed TRANSPOSED so that lane&31 is the query:
-//   S^T[key][q]  = mfma32x32x16(A = K rows,   B = Q rows)      -> a lane holds 32 of the 64 scores of ITS query
-//   O^T[d][q]   += mfma32x32x16(A = V^T rows, B = P^T)         -> P^T is consumed straight from the S^T
-// registers (the MFMA C layout of S^T is a valid B-operand layout once V^T's keys are read in the matching
-// permuted order: two ds_read_b64 per fragment), running max / sum / rescale are lane-local, and the only
-// cross-lane traffic of the online softmax is one exchange with lane^32.
+// the 4 waves, everything computed transposed.  tg_attn_fwd.h explains the formulation, the swizzle, the key
+// permutation, the permlane exchange and the lazy running max, and holds the pieces shared with tg_attention_wide.hip
+// and tg_attention_relpos.hip.  Every kernel of THIS file must keep its assembly when such a piece moves
+// (scripts/dev_isa_diff.py): a piece that does not survive the move keeps its copy here and names the header function.
 // head_dim 40 / 80 (SD-1.5) are zero-padded to 48 / 80 for QK^T (K of the MFMA) and 64 / 96 rows for PV.
-#include "tg_common.h"
+#include "tg_attn_fwd.h"
 
 namespace {
 
 constexpr int KV = 64;        // keys per tile
 
-// LDS-DMA sources for out-of-range pieces: head-dim / key padding reads zeros; the "ones row" (below) reads 1.0
-__device__ __attribute__((aligned(256))) unsigned char attn_zero_page[256];
-#define TG_R8(x) x, x, x, x, x, x, x, x
-__device__ __attribute__((aligned(256))) const unsigned short attn_ones_bf16[64] = {TG_R8(TG_R8(0x3F80))};
-__device__ __attribute__((aligned(256))) const unsigned short attn_ones_f16[64] = {TG_R8(TG_R8(0x3C00))};
 // FOLD variants: K's first padding column (d = head dim) is fed 1.0 so that the QK^T MFMA adds the query's running-max bias
 __device__ __attribute__((aligned(256))) const unsigned short attn_one0_bf16[8] = {0x3F80, 0, 0, 0, 0, 0, 0, 0};
 __device__ __attribute__((aligned(256))) const unsigned short attn_one0_f16[8] = {0x3C00, 0, 0, 0, 0, 0, 0, 0};
 template <typename T> __device__ __forceinline__ const T* one0_page();
 template <> __device__ __forceinline__ const bf16_t* one0_page<bf16_t>() { return reinterpret_cast<const bf16_t*>(attn_one0_bf16); }
 template <> __device__ __forceinline__ const f16_t* one0_page<f16_t>() { return reinterpret_cast<const f16_t*>(attn_one0_f16); }
-template <typename T> __device__ __forceinline__ const T* ones_page();
-template <> __device__ __forceinline__ const bf16_t* ones_page<bf16_t>() { return reinterpret_cast<const bf16_t*>(attn_ones_bf16); }
-template <> __device__ __forceinline__ const f16_t* ones_page<f16_t>() { return reinterpret_cast<const f16_t*>(attn_ones_f16); }
 
 struct AttnParams {
   int heads, hd, n_q, n_qblk;
@@ -56,14 +46,11 @@ struct AttnParams {
   float inv_scale;
 };
 
-// Data path: K tile = NP panels of [64 keys][64 d] and V^T tile = [DV d][64 keys], both as 128-byte LDS rows filled by
-// LDS-DMA (global_load_lds_dwordx4, no VGPR round trip, no ds_write pass) with the GEMM's XOR swizzle (16-byte slot ^
-// ((row >> 1) & 7), applied on the source address and again on the fragment read).  Two stages: the DMA of tile t+1
-// is in flight while tile t is multiplied, one barrier per tile.
-// ONES (variants whose DV exceeds the head dim): V^T row DV-1 is fed from a page of 1.0, so the PV MFMA itself
-// accumulates the softmax denominator l = sum_k p[k] in accumulator row DV-1 (rescaled with O for free) and the 32
-// per-tile v_add_f32 of the row sum disappear — the loop is VALU-bound (32 v_exp_f32 at quarter rate + ~100 other
-// VALU ops against 14 MFMAs per wave-tile at head dim 40), so every removed VALU instruction counts.
+// Data path: K tile = NP panels of [64 keys][64 d] and V^T tile = [DV d][64 keys], swizzled 128-byte LDS rows filled by
+// LDS-DMA.  Two stages: the DMA of tile t+1 is in flight while tile t is multiplied, one barrier per tile.
+// ONES (variants whose DV exceeds the head dim; attn_row_sum): the PV MFMA accumulates the softmax denominator — the loop
+// is VALU-bound (32 v_exp_f32 at quarter rate + ~100 other VALU ops against 14 MFMAs per wave-tile at head dim 40), so
+// every removed VALU instruction counts.
 // FOLD (head dim = DPAD - 8, i.e. 40 -> 48: the SD-1.5 level-0 layers that dominate attention time): the loop is VALU-bound and a
 // quarter of its VALU instructions were the `fma(s, scale, -max)` in front of every exp2.  Q is pre-multiplied by scale * log2(e)
 // once per block, and the spare K column of the padded QK^T contraction carries 1.0 while the query's spare element carries
@@ -76,7 +63,6 @@ struct AttnParams {
 template <typename T, int DPAD, int DV, bool ONES, bool FOLD, bool MASK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 3 : (DV <= 96 ? 2 : 1)))) void attention_kernel(AttnParams p) {
   typedef typename Vec<T>::v8 V8;
-  typedef typename Vec<T>::v4 V4;
   constexpr int NP = (DPAD + 63) / 64;          // K panels
   constexpr int NKS = DPAD / 16;
   constexpr int DT = DV / 32;
@@ -90,13 +76,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
 
   const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // XCD-aware block order (speed only): block b runs on XCD b % 8; give each XCD a contiguous chunk of the
-  // (batch, head, q-block) space so that all q-blocks of one (batch, head) share K / V^T through ONE private L2.
-  int lbid;
-  {
-    const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, xcd = blockIdx.x & 7;
-    lbid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  }
+  const int lbid = attn_xcd_block();             // over (batch, head, q-block), q-block fastest
   const int qblk = lbid % p.n_qblk;
   const int h = (lbid / p.n_qblk) % p.heads, b = lbid / (p.n_qblk * p.heads);
   const int HD = p.hd;
@@ -110,10 +90,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
       const int d = ks * 16 + hi * 8;
-      V8 v;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = from_f32<T>(0.f);
-      if (q_ok && d < HD) v = *reinterpret_cast<const V8*>(qp + d);
+      V8 v = attn_q_frag(qp + d, q_ok && d < HD);
       if constexpr (FOLD) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = from_f32<T>(to_f32<T>(v[j]) * p.scale_log2);
@@ -133,10 +110,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
   // ---- LDS-DMA tile loader
   const int lrow_lane = lane >> 3, slot_lane = lane & 7;
   const T* zero = reinterpret_cast<const T*>(attn_zero_page);
-  auto dma = [&](const T* src, T* lds_row_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_row_base, 16, 0, 0);
-  };
+  // mirrors attn_issue_tile (tg_attn_fwd.h), plus the FOLD page
   auto issue = [&](const T* kb, long k_ld, const T* vb, long vt_ld, int len, int kv0, int stage) {
     T* sK = sbase + stage * STAGE;
     T* sV = sK + K_ELEMS;
@@ -154,7 +128,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
       const bool ok = d0 < HD && kv0 + r < len;
       const T* src = ok ? kb + (long)(kv0 + r) * k_ld + d0 : zero;
       if (FOLD && d0 == HD) src = one0_page<T>();
-      dma(src, sK + q * 512);
+      attn_dma16(src, sK + q * 512);
     }
 #pragma unroll
     for (int j = 0; j < VJ; ++j) {
@@ -163,7 +137,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
       const int c0 = kv0 + ((slot ^ ((d >> 1) & 7)) << 3);
       const T* src = (d < HD && c0 < len) ? vb + (long)d * vt_ld + c0 : zero;
       if (ONES && d == DV - 1) src = ones_page<T>();
-      dma(src, sV + q * 512);
+      attn_dma16(src, sV + q * 512);
     }
   };
   // FULL tiles of segment 0 (kv0 + KV <= len0, not causal): nothing of a request's source address changes from tile to tile except a
@@ -204,9 +178,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
     T* sK = sbase + stage * STAGE;
     T* sV = sK + K_ELEMS;
 #pragma unroll
-    for (int j = 0; j < KJ; ++j) dma(kp[j], sK + (j * 4 + wave) * 512);
+    for (int j = 0; j < KJ; ++j) attn_dma16(kp[j], sK + (j * 4 + wave) * 512);
 #pragma unroll
-    for (int j = 0; j < VJ; ++j) dma(vp[j], sV + (j * 4 + wave) * 512);
+    for (int j = 0; j < VJ; ++j) attn_dma16(vp[j], sV + (j * 4 + wave) * 512);
   };
   // on to the next tile.  Once per staged tile of segment 0, full or not and outside any branch (a branch around it is what makes the allocator
   // split the pointers' registers); pointers that have run past the last full tile are not used again
@@ -221,45 +195,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
     if (fast && kv0 + KV <= p.len0) issue_full(stage);
     else issue(kb0, p.k0_ld, vb0, p.vt0_ld, p.len0, kv0, stage);
   };
-  // a 16-byte V^T chunk that straddles `len` brought columns >= len along (they may hold anything, and 0 * NaN = NaN
-  // in the PV MFMA): zero them in LDS.  Only ragged tiles (text 77 = 64 + 13 keys, 4 image tokens) take this path.
+  // the V^T fix-up of a ragged tile: only text 77 = 64 + 13 keys and 4 image tokens take this path
   auto fixup_v = [&](int rem, int stage) {
-    T* sV = sbase + stage * STAGE + K_ELEMS;
-    if (tid < DV && tid < HD) {
-      const int d = tid, ch = rem >> 3;
-      T* rowp = sV + d * 64 + ((ch ^ ((d >> 1) & 7)) << 3);
-      for (int c = rem & 7; c < 8; ++c) rowp[c] = from_f32<T>(0.f);
-    }
+    if (tid < DV && tid < HD) attn_zero_vt_tail(sbase + stage * STAGE + K_ELEMS, tid, rem);
   };
 
   const int skey = (l31 >> 1) & 7;                       // swizzle key of this lane's fragment rows
-  // per-lane LDS element offsets of the fragment reads, computed ONCE (they only depend on the lane): inside the loop an
-  // access is (stage base + table entry + compile-time constant) instead of re-deriving xor / shift / add per read
-  // KEY PERMUTATION: MFMA row i of a 32-key score tile is fed K row perm(i) = i with bits 2 and 3 swapped.  The 32x32
-  // accumulator gives lane-half `hi` the rows 8g + 4 hi + j in registers 4g + j; with the permutation registers
-  // 8cc .. 8cc+7 hold the 8 CONSECUTIVE keys 16cc + 8 hi + 0..7, i.e. the P^T fragment of the PV MFMA pairs with ONE
-  // 16-byte V^T slot (a single ds_read_b128 per fragment, no register shuffles) instead of two 8-byte halves of
-  // neighbouring slots.
-  const int prow = (l31 & 19) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
+  // per-lane LDS element offsets of the fragment reads (the keys are derived here, in this order: the assembly depends on it)
+  const int prow = attn_perm_row(l31);
   const int pkey = (prow >> 1) & 7;
   int kofs[4], vofs[4];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) kofs[c] = prow * 64 + (((2 * c + hi) ^ pkey) << 3);
+  for (int c = 0; c < 4; ++c) kofs[c] = attn_frag_ofs(prow, pkey, c, hi);
 #pragma unroll
-  for (int c = 0; c < 4; ++c) vofs[c] = l31 * 64 + (((2 * c + hi) ^ skey) << 3);
+  for (int c = 0; c < 4; ++c) vofs[c] = attn_frag_ofs(l31, skey, c, hi);
   // RAW scores of one 64-key tile for this lane's query (the softmax scale is folded into the exp2 argument by one
   // fma per element); keys >= len are masked to -inf only on a ragged tile, full tiles take no compare/select at all.
   auto scores = [&](f32x16 (&s)[2], const T* sK, int len, int kv0, bool causal) {
-#pragma unroll
-    for (int kvt = 0; kvt < 2; ++kvt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[kvt][r] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) {
-        V8 kf = *reinterpret_cast<const V8*>(sK + kofs[ks & 3] + ((ks >> 2) * 4096 + kvt * 32 * 64));
-        s[kvt] = mfma32(kf, qf[ks], s[kvt]);
-      }
-    }
+    attn_qk<T>(s, sK, qf, kofs);
     if (kv0 + KV > len || causal) {
       // ragged tile and / or causal mask (key j visible to query i iff j <= i: key 0 is always visible, so a row's running
       // max is finite from the first tile on and fully masked later tiles contribute exp2(-inf) = 0)
@@ -271,38 +224,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
           const int kv = kv0 + kvt * 32 + 16 * (r >> 3) + 8 * hi + (r & 7);     // key held by register r (permuted rows)
           if (kv >= len || kv > qmax) s[kvt][r] = -INFINITY;
         }
-    }
-  };
-
-  auto tile_max = [&](const f32x16 (&s)[2]) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kvt = 0; kvt < 2; ++kvt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kvt][r]);
-    // the other 32-key half of the row lives in lane ^ 32: v_permlane32_swap exchanges the upper 32 lanes of one copy
-    // with the lower 32 of the other (no LDS round trip, unlike the ds_bpermute behind __shfl_xor)
-    // (inline asm: with the builtin hipcc drops the second result and the max with it; s_nop covers the VALU-write ->
-    // permlane-read hazard the assembler does not see)
-    float a = mx, b = mx;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return fmaxf(a, b);
-  };
-
-  // O^T += V^T * P^T for one tile; P^T comes straight from the score registers: chunk c covers keys
-  // kvt*32 + 16*cc + 8*hi + 0..7 = 16-byte slot 4*kvt + 2*cc + hi of the V^T row
-  auto pv = [&](const f32x16 (&s)[2], const T* sV) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int kvt = c >> 1, cc = c & 1;
-      V8 pf;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pf[j] = from_f32<T>(s[kvt][8 * cc + j]);
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        const V8 vf = *reinterpret_cast<const V8*>(sV + vofs[c] + t * 32 * 64);
-        o[t] = mfma32(vf, pf, o[t]);
-      }
     }
   };
 
@@ -337,16 +258,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
           if (kv < p.len0) s[kvt][r] += mp[kv] * p.inv_scale;
         }
     }
-    const float tm = tile_max(s);
+    const float tm = attn_tile_max(s);
     // m_run is kept in RAW score units; exp2 arguments are formed as fma(s, c, -m*c) with c = scale * log2(e) > 0.
     // v_exp_f32 directly (__builtin_amdgcn_exp2f): results stay far inside the fp32 range, exp2(-inf) = 0 — none of
     // exp2f()'s denormal-range rescaling (v_ldexp + compares + selects per element) is needed.
-    // LAZY RUNNING MAX: softmax is invariant to the reference point, so m_run only moves (and O is only rescaled: 32
-    // accumulator multiplies per tile) when some row's tile max exceeds it by more than LAZY_LOG2 in exp2 units; until
-    // then probabilities are formed against the stale reference and are at most 2^LAZY_LOG2 (bf16 P and the fp32
-    // accumulators have the range).  With a strict "any row has a new max" test the rescale ran on most tiles: over 32
-    // rows a new maximum keeps turning up somewhere.
-    constexpr float LAZY_LOG2 = 8.f;
+    // The reference moves lazily (LAZY_LOG2); the generic branch mirrors attn_lazy_max, the rescale loops attn_scale_acc
     float ps = 0.f;
     float mc = 0.f;                                  // generic path: the reference in exp2 units
     if constexpr (FOLD) {
@@ -393,18 +309,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
         if (!ONES) ps += e;
       }
     if (!ONES) l_run += ps;
-    pv(s, sV);
+    attn_pv<T, 32 * 64>(o, s, sV, vofs);
   }
   {
-    float l_tot;
-    if (ONES) {
-      // accumulator row DV-1 = tile DT-1, register 15 of the lanes with hi = 1
-      const float c = hi ? o[DT - 1][15] : 0.f;
-      l_tot = c + __shfl_xor(c, 32, 64);
-    } else {
-      l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    }
-    const float inv = 1.f / l_tot;
+    const float inv = 1.f / attn_row_sum<ONES>(o, l_run, hi);
 #pragma unroll
     for (int t2 = 0; t2 < DT; ++t2)
 #pragma unroll
@@ -427,7 +335,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
     }
     scores(s, sK, p.len1, 0, false);
     const float sc1 = FOLD ? 1.0f : p.scale_log2;           // FOLD: the scores are already in log2 units
-    const float mc1 = tile_max(s) * sc1;
+    const float mc1 = attn_tile_max(s) * sc1;
     float ps = 0.f;
 #pragma unroll
     for (int kvt = 0; kvt < 2; ++kvt)
@@ -445,25 +353,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
     for (int kvt = 0; kvt < 2; ++kvt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[kvt][r] *= f;
-    pv(s, sK + K_ELEMS);
+    attn_pv<T, 32 * 64>(o, s, sK + K_ELEMS, vofs);
   }
 
   // ---------------- store: O^T regs -> out[b, q, h*HD + d], 4 consecutive d per 8-byte store
-  if (q_ok) {
-    T* op = reinterpret_cast<T*>(p.out) + (long)b * p.out_bs + qrow * p.out_ld + (long)h * HD;
-#pragma unroll
-    for (int t = 0; t < DT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * hi;
-        if (d < HD) {
-          V4 v;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = from_f32<T>(o[t][4 * g + j]);
-          *reinterpret_cast<V4*>(op + d) = v;
-        }
-      }
-  }
+  if (q_ok) attn_store(o, reinterpret_cast<T*>(p.out) + (long)b * p.out_bs + qrow * p.out_ld + (long)h * HD, hi, HD);
 }
 
 template <typename T, int DPAD, int DV, bool ONES, bool FOLD = false, bool MASK = false>

@@ -7,8 +7,8 @@
 // them to the fp32 scores tile by tile, in registers.
 //
 // The attention kernel is tg_attention.hip's generic (non-FOLD) instance with the bias in place of the materialised mask: same block (4 waves x 32
-// queries), same LDS-DMA K / V^T tiles with the XOR swizzle, same transposed products (lane & 31 = the query), same lazy running max.  What it needs
-// of that file is COPIED here (sharing a header would re-instantiate its kernels in another context and move their register allocation).
+// queries), same LDS-DMA K / V^T tiles with the XOR swizzle, same transposed products (lane & 31 = the query), same lazy running max.  Those pieces
+// are tg_attn_fwd.h's (read its header first); this file keeps the bias registers and the unrolled G = 14 tiles.
 // Scores are kept in exp2 units from the bias add on:  x = fma(q.k, s log2 e, bias log2 e);  p = exp2(x - m).
 //   G = 64: a 64-key tile is one grid row kh = t, so Bh is ONE value per query per tile (loaded one tile ahead of its use, before the next tile's
 //           DMA is issued) and the lane's 32 Bw values are the same for every tile: 32 registers, loaded once.
@@ -17,20 +17,12 @@
 //           keys here (they carry the projection bias and their table entries): only keys >= 196 are masked.
 // Occupancy: d = 64 keeps the parent's three waves per SIMD (164 VGPRs with the 32 bias registers), d = 80 its two (192 / 206 VGPRs); the attribute
 // below only sets the floor of two.  No scratch in any instance (build.py gate).
-#include "tg_common.h"
+#include "tg_attn_fwd.h"
 
 namespace {
 
 constexpr int KV = 64;        // keys per tile
 constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ __attribute__((aligned(256))) unsigned char rp_zero_page[256];
-#define TG_RP8(x) x, x, x, x, x, x, x, x
-__device__ __attribute__((aligned(256))) const unsigned short rp_ones_bf16[64] = {TG_RP8(TG_RP8(0x3F80))};
-__device__ __attribute__((aligned(256))) const unsigned short rp_ones_f16[64] = {TG_RP8(TG_RP8(0x3C00))};
-template <typename T> __device__ __forceinline__ const T* rp_ones_page();
-template <> __device__ __forceinline__ const bf16_t* rp_ones_page<bf16_t>() { return reinterpret_cast<const bf16_t*>(rp_ones_bf16); }
-template <> __device__ __forceinline__ const f16_t* rp_ones_page<f16_t>() { return reinterpret_cast<const f16_t*>(rp_ones_f16); }
 
 struct RelposParams {
   int heads, n_q, n_qblk;
@@ -44,19 +36,16 @@ struct RelposParams {
 };
 
 // <T, DPAD, DV, ONES, G>: head dim 64 = <64, 64, false>, head dim 80 = <80, 96, true> (V^T row 95 is fed 1.0: the PV MFMA accumulates the softmax
-// denominator, as in tg_attention.hip)
+// denominator)
 template <typename T, int DPAD, int DV, bool ONES, int G>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void attention_relpos_kernel(RelposParams p) {
   typedef typename Vec<T>::v8 V8;
-  typedef typename Vec<T>::v4 V4;
   constexpr int HD = ONES ? DV - 16 : DV;       // 80 or 64
   constexpr int LEN = G * G;
   constexpr int NT = (LEN + KV - 1) / KV;
   constexpr int NP = (DPAD + 63) / 64;          // K panels
   constexpr int NKS = DPAD / 16;
   constexpr int DT = DV / 32;
-  constexpr int KJ = NP * 2;
-  constexpr int VJ = DV / 32;
   constexpr int K_ELEMS = NP * 64 * 64;
   constexpr int STAGE = K_ELEMS + DV * 64;
   static_assert(HD == 64 || HD == 80, "head dim 64 or 80");
@@ -67,11 +56,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
 
   const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int lbid;                                      // XCD-aware block order (speed only): the q-blocks of one (batch, head) share K / V^T through one L2
-  {
-    const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, xcd = blockIdx.x & 7;
-    lbid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  }
+  const int lbid = attn_xcd_block();             // over (batch, head, q-block), q-block fastest
   const int qblk = lbid % p.n_qblk;
   const int h = (lbid / p.n_qblk) % p.heads, b = lbid / (p.n_qblk * p.heads);
   const long qrow = (long)qblk * 128 + wave * 32 + l31;
@@ -83,11 +68,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
       const int d = ks * 16 + hi * 8;
-      V8 v;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = from_f32<T>(0.f);
-      if (q_ok && d < HD) v = *reinterpret_cast<const V8*>(qp + d);
-      qf[ks] = v;
+      qf[ks] = attn_q_frag(qp + d, q_ok && d < HD);
     }
   }
 
@@ -125,95 +106,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;          // m_run: exp2 units
 
-  // ---- LDS-DMA tile loader (tg_attention.hip)
-  const int lrow = lane >> 3, slot = lane & 7;
-  const T* zero = reinterpret_cast<const T*>(rp_zero_page);
-  auto dma = [&](const T* src, T* lds_row_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_row_base, 16, 0, 0);
-  };
-  auto issue = [&](const T* kb, long k_ld, const T* vb, long vt_ld, int kv0, int stage) {
-    T* sK = sbase + stage * STAGE;
-    T* sV = sK + K_ELEMS;
-#pragma unroll
-    for (int j = 0; j < KJ; ++j) {
-      const int q = j * 4 + wave;                       // rows [8q, 8q+8) of the panel stack
-      const int prow = 8 * q + lrow;
-      const int r = prow & 63, panel = prow >> 6;
-      const int d0 = panel * 64 + ((slot ^ ((r >> 1) & 7)) << 3);
-      const bool ok = d0 < HD && kv0 + r < LEN;
-      const T* src = ok ? kb + (long)(kv0 + r) * k_ld + d0 : zero;
-      dma(src, sK + q * 512);
-    }
-#pragma unroll
-    for (int j = 0; j < VJ; ++j) {
-      const int q = j * 4 + wave;
-      const int d = 8 * q + lrow;
-      const int c0 = kv0 + ((slot ^ ((d >> 1) & 7)) << 3);
-      const T* src = (d < HD && c0 < LEN) ? vb + (long)d * vt_ld + c0 : zero;
-      if (ONES && d == DV - 1) src = rp_ones_page<T>();
-      dma(src, sV + q * 512);
-    }
-  };
-  // the 16-byte V^T chunk that straddles key 196 brought 4 columns past the window along (0 * NaN = NaN in the PV MFMA): zero them in LDS
-  auto fixup_v = [&](int rem, int stage) {
-    T* sV = sbase + stage * STAGE + K_ELEMS;
-    if (tid < HD) {
-      const int d = tid, ch = rem >> 3;
-      T* rowp = sV + d * 64 + ((ch ^ ((d >> 1) & 7)) << 3);
-      for (int c = rem & 7; c < 8; ++c) rowp[c] = from_f32<T>(0.f);
-    }
-  };
-
-  const int skey = (l31 >> 1) & 7;
-  // KEY PERMUTATION (tg_attention.hip): registers 8cc .. 8cc+7 of s[kvt] hold the 8 consecutive keys 32 kvt + 16 cc + 8 hi + 0..7
-  const int prow = (l31 & 19) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
-  const int pkey = (prow >> 1) & 7;
-  int kofs[4], vofs[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) kofs[c] = prow * 64 + (((2 * c + hi) ^ pkey) << 3);
-#pragma unroll
-  for (int c = 0; c < 4; ++c) vofs[c] = l31 * 64 + (((2 * c + hi) ^ skey) << 3);
-
-  auto tile_max = [&](const f32x16 (&s)[2]) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kvt = 0; kvt < 2; ++kvt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kvt][r]);
-    float a = mx, bb = mx;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(bb));
-    return fmaxf(a, bb);
-  };
-
-  auto pv = [&](const f32x16 (&s)[2], const T* sV) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int kvt = c >> 1, cc = c & 1;
-      V8 pf;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pf[j] = from_f32<T>(s[kvt][8 * cc + j]);
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        const V8 vf = *reinterpret_cast<const V8*>(sV + vofs[c] + t * 32 * 64);
-        o[t] = mfma32(vf, pf, o[t]);
-      }
-    }
-  };
-
   const T* kb0 = reinterpret_cast<const T*>(p.k0) + (long)b * p.k0_bs + (long)h * HD;
   const T* vb0 = reinterpret_cast<const T*>(p.vt0) + (long)b * p.vt0_bs + (long)h * HD * p.vt0_ld;
+  // ---- LDS-DMA tile loader
+  const int lrow = lane >> 3, slot = lane & 7;
+  auto issue = [&](int kv0, int stage) {
+    T* sK = sbase + stage * STAGE;
+    attn_issue_tile<T, NP, DV, ONES>(sK, sK + K_ELEMS, kb0, p.k0_ld, vb0, p.vt0_ld, LEN, kv0, HD, wave, lrow, slot);
+  };
+
+  const int prow = attn_perm_row(l31);
+  int kofs[4], vofs[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) kofs[c] = attn_frag_ofs(prow, (prow >> 1) & 7, c, hi);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) vofs[c] = attn_frag_ofs(l31, (l31 >> 1) & 7, c, hi);
 
   float bh_nxt = 0.f;
   if constexpr (G == 64) bh_nxt = bhp[0];
-  issue(kb0, p.k0_ld, vb0, p.vt0_ld, 0, 0);
+  issue(0, 0);
 
   auto tile = [&](const int t) __attribute__((always_inline)) {
     const int st = t & 1, kv0 = t * KV;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (kv0 + KV > LEN && ((LEN - kv0) & 7)) {
-      fixup_v(LEN - kv0, st);
+    if (kv0 + KV > LEN && ((LEN - kv0) & 7)) {           // the chunk that straddles key 196 brought 4 columns past the window along
+      if (tid < HD) attn_zero_vt_tail(sbase + st * STAGE + K_ELEMS, tid, LEN - kv0);
       __syncthreads();
     }
     float bh_t = 0.f;
@@ -221,19 +139,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
       bh_t = bh_nxt * LOG2E;
       if (t + 1 < NT) bh_nxt = bhp[t + 1];             // before the DMA of tile t + 1: consumed after the wait at the top of the next tile
     }
-    if (t + 1 < NT) issue(kb0, p.k0_ld, vb0, p.vt0_ld, kv0 + KV, st ^ 1);
+    if (t + 1 < NT) issue(kv0 + KV, st ^ 1);
     const T* sK = sbase + st * STAGE;
     f32x16 s[2];
-#pragma unroll
-    for (int kvt = 0; kvt < 2; ++kvt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[kvt][r] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) {
-        V8 kf = *reinterpret_cast<const V8*>(sK + kofs[ks & 3] + ((ks >> 2) * 4096 + kvt * 32 * 64));
-        s[kvt] = mfma32(kf, qf[ks], s[kvt]);
-      }
-    }
+    attn_qk<T>(s, sK, qf, kofs);
     // x = s * (scale log2 e) + bias log2 e, fp32
 #pragma unroll
     for (int kvt = 0; kvt < 2; ++kvt)
@@ -260,18 +169,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
           if (kv >= LEN) s[kvt][r] = -INFINITY;
         }
     }
-    const float tm = tile_max(s);
-    constexpr float LAZY_LOG2 = 8.f;                    // lazy running max (tg_attention.hip): P stays <= 2^8 against a stale reference
-    if (__any(tm > m_run + LAZY_LOG2)) {
-      const float m_new = fmaxf(m_run, tm);
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-#pragma unroll
-      for (int t2 = 0; t2 < DT; ++t2)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[t2][r] *= alpha;
-      if (!ONES) l_run *= alpha;
-      m_run = m_new;
-    }
+    attn_lazy_max<ONES>(o, m_run, l_run, attn_tile_max(s), 1.f);
     float ps = 0.f;
 #pragma unroll
     for (int kvt = 0; kvt < 2; ++kvt)
@@ -282,7 +180,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
         if (!ONES) ps += e;
       }
     if (!ONES) l_run += ps;
-    pv(s, sK + K_ELEMS);
+    attn_pv<T, 32 * 64>(o, s, sK + K_ELEMS, vofs);
   };
 
   if constexpr (G == 14) {
@@ -298,36 +196,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     for (int t = 0; t < NT; ++t) tile(t);
   }
 
-  {
-    float l_tot;
-    if (ONES) {
-      const float c = hi ? o[DT - 1][15] : 0.f;          // accumulator row DV - 1
-      l_tot = c + __shfl_xor(c, 32, 64);
-    } else {
-      l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    }
-    const float inv = 1.f / l_tot;
-#pragma unroll
-    for (int t2 = 0; t2 < DT; ++t2)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[t2][r] *= inv;
-  }
-
-  if (q_ok) {
-    T* op = reinterpret_cast<T*>(p.out) + (long)b * p.out_bs + qrow * p.out_ld + (long)h * HD;
-#pragma unroll
-    for (int t = 0; t < DT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * hi;
-        if (d < HD) {
-          V4 v;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = from_f32<T>(o[t][4 * g + j]);
-          *reinterpret_cast<V4*>(op + d) = v;
-        }
-      }
-  }
+  attn_scale_acc(o, 1.f / attn_row_sum<ONES>(o, l_run, hi));
+  if (q_ok) attn_store(o, reinterpret_cast<T*>(p.out) + (long)b * p.out_bs + qrow * p.out_ld + (long)h * HD, hi, HD);
 }
 
 template <typename T, int DPAD, int DV, bool ONES, int G>

@@ -6,10 +6,8 @@
 // [n_q, len] exists in memory; scores are fp32 from the stored Q and K, the softmax is online (running max / sum in fp32), P is rounded to the storage dtype
 // where it enters the PV product (as tg_attention does) and O is accumulated in fp32 and rounded once.
 //
-// Same formulation as tg_attention.hip (read its header first): everything is computed TRANSPOSED so that lane & 31 is the query,
-//   S^T[key][q]  = mfma32x32x16(A = K rows,   B = Q rows)
-//   O^T[d][q]   += mfma32x32x16(A = V^T rows, B = P^T)         P^T straight from the S^T registers (permuted key rows, one ds_read_b128 per fragment)
-// block = 4 waves x 32 queries, K and V^T tiles staged once per block by LDS-DMA and shared by the four waves, two stages.
+// The formulation and its shared pieces are tg_attn_fwd.h's (read its header first), with KVT = 1: tiles of 32 keys.  This file keeps the column
+// parts, the V^T image of d pairs, the key split and the combine.
 //
 // What differs is the budget.  One wave per SIMD (the unified 512-register file): a wave's Q fragment is D / 4 registers (128 at d = 512) and its
 // O^T accumulator DO / 2 (256 for all 512 columns) — with the score tile, fragments and addresses the full-width d = 512 accumulator leaves the
@@ -35,15 +33,13 @@
 // The hand-off is the kernel boundary: per-XCD L2s are not coherent inside a launch, and in-launch device-scope hand-offs measured -4 / -7 % here
 // (README, round 5), so there is no arrival counter, no atomic and no "last block combines".  Block order: column part fastest, then query block,
 // then split, head, batch, so the blocks that read one (batch, head, split)'s K / V^T range are contiguous and fall into one XCD chunk.
-#include "tg_common.h"
+#include "tg_attn_fwd.h"
 
 #include <cstdlib>
 
 namespace {
 
 constexpr int WKV = 32;        // keys per tile
-
-__device__ __attribute__((aligned(256))) unsigned char attn_wide_zero_page[256];
 
 struct WideParams {
   int heads, n_q, n_qblk;
@@ -70,7 +66,6 @@ template <typename T, int D, int DO, bool SPLIT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void attention_wide_kernel(WideParams p) {
   typedef __attribute__((ext_vector_type(2))) float f32x2;
   typedef typename Vec<T>::v8 V8;
-  typedef typename Vec<T>::v4 V4;
   constexpr int NP = D / 64;                    // K panels
   constexpr int NKS = D / 16;
   constexpr int DT = DO / 32;
@@ -86,13 +81,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void a
 
   const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // XCD-aware block order (speed only, as tg_attention): each XCD gets a contiguous chunk of the (batch, head, q-block, column part) space, so the
-  // blocks that read one (batch, head)'s K / V^T share ONE private L2
-  int lbid;
-  {
-    const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, xcd = blockIdx.x & 7;
-    lbid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  }
+  const int lbid = attn_xcd_block();             // over (batch, head, [split,] q-block, column part), column part fastest
   const int dbase = (lbid % NSPLIT) * DO;        // first output column of this block
   const int lq = lbid / NSPLIT;
   const int qblk = lq % p.n_qblk;
@@ -114,13 +103,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void a
   {
     const T* qp = reinterpret_cast<const T*>(p.q) + (long)b * p.q_bs + qrow * p.q_ld + (long)h * D;
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      V8 v;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = from_f32<T>(0.f);
-      if (q_ok) v = *reinterpret_cast<const V8*>(qp + ks * 16 + hi * 8);
-      qf[ks] = v;
-    }
+    for (int ks = 0; ks < NKS; ++ks) qf[ks] = attn_q_frag(qp + ks * 16 + hi * 8, q_ok);
   }
 
   f32x16 o[DT];
@@ -132,11 +115,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void a
 
   // ---- LDS-DMA tile loader
   const int lrow = lane >> 3, slot = lane & 7;
-  const T* zero = reinterpret_cast<const T*>(attn_wide_zero_page);
-  auto dma = [&](const T* src, T* lds_row_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_row_base, 16, 0, 0);
-  };
+  const T* zero = reinterpret_cast<const T*>(attn_zero_page);
   const T* kb = reinterpret_cast<const T*>(p.k) + (long)b * p.k_bs + (long)h * D;
   const T* vb = reinterpret_cast<const T*>(p.vt) + (long)b * p.vt_bs + ((long)h * D + dbase) * p.vt_ld;
   auto issue = [&](int kv0, int stage) {
@@ -149,7 +128,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void a
       const int r = prow & 31, panel = prow >> 5;
       const int d0 = panel * 64 + ((slot ^ ((r >> 1) & 7)) << 3);
       const T* src = kv0 + r < p.len ? kb + (long)(kv0 + r) * p.k_ld + d0 : zero;
-      dma(src, sK + q * 512);
+      attn_dma16(src, sK + q * 512);
     }
 #pragma unroll
     for (int j = 0; j < VJ; ++j) {
@@ -159,18 +138,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void a
       const int d = 2 * R + (ls >> 2);
       const int c0 = kv0 + ((ls & 3) << 3);
       const T* src = c0 < p.len ? vb + (long)d * p.vt_ld + c0 : zero;
-      dma(src, sV + q * 512);
+      attn_dma16(src, sV + q * 512);
     }
   };
 
-  // per-lane LDS element offsets of the fragment reads (they only depend on the lane).  KEY PERMUTATION as in tg_attention.hip: MFMA row i of the score
-  // tile is fed K row perm(i) = i with bits 2 and 3 swapped, so accumulator registers 8c .. 8c+7 hold the 8 CONSECUTIVE keys 16c + 8 hi + 0..7 and the
-  // P^T fragment of chunk c pairs with ONE 16-byte V^T slot
-  const int prow = (l31 & 19) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
-  const int pkey = (prow >> 1) & 7;
+  // per-lane LDS element offsets of the fragment reads; V^T: LDS row l31 >> 1 holds d = l31 in slots 4 (l31 & 1) .. + 3
+  const int prow = attn_perm_row(l31);
   int kofs[4], vofs[2];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) kofs[c] = prow * 64 + (((2 * c + hi) ^ pkey) << 3);
+  for (int c = 0; c < 4; ++c) kofs[c] = attn_frag_ofs(prow, (prow >> 1) & 7, c, hi);
 #pragma unroll
   for (int c = 0; c < 2; ++c) vofs[c] = (l31 >> 1) * 64 + (((((l31 & 1) << 2) + 2 * c + hi) ^ ((l31 >> 2) & 7)) << 3);
 
@@ -188,64 +164,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void a
     const T* sV = sK + K_ELEMS;
 
     // RAW scores of the 32-key tile for this lane's query: register r holds key kv0 + 16 (r >> 3) + 8 hi + (r & 7)
-    f32x16 s;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      const V8 kf = *reinterpret_cast<const V8*>(sK + kofs[ks & 3] + (ks >> 2) * 2048);
-      s = mfma32(kf, qf[ks], s);
-    }
+    f32x16 s[1];
+    attn_qk<T>(s, sK, qf, kofs);
     if (kv0 + WKV > p.len) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (kv0 + 16 * (r >> 3) + 8 * hi + (r & 7) >= p.len) s[r] = -INFINITY;
+        if (kv0 + 16 * (r >> 3) + 8 * hi + (r & 7) >= p.len) s[0][r] = -INFINITY;
     }
-    float tm;
-    {
-      float mx = -INFINITY;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[r]);
-      // the other 16 keys of the row live in lane ^ 32 (inline asm and s_nop: see tile_max in tg_attention.hip)
-      float a = mx, b2 = mx;
-      asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b2));
-      tm = fmaxf(a, b2);
-    }
-    // m_run in RAW score units, exp2 arguments fma(s, c, -m c) with c = scale * log2(e) > 0.  LAZY RUNNING MAX as in tg_attention.hip: O (DO / 2
-    // accumulator registers, through v_accvgpr moves) is only rescaled when some row's tile max exceeds the reference by more than 2^LAZY_LOG2;
-    // until then probabilities are at most 2^8 against the stale reference, which P's storage dtype and the fp32 accumulators hold
-    constexpr float LAZY_LOG2 = 8.f;
-    if (__any(tm * p.scale_log2 > m_run * p.scale_log2 + LAZY_LOG2)) {
-      const float m_new = fmaxf(m_run, tm);
-      const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);     // first tile: exp2(-inf) = 0 on a zero accumulator
-#pragma unroll
-      for (int t2 = 0; t2 < DT; ++t2)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[t2][r] *= alpha;
-      l_run *= alpha;
-      m_run = m_new;
-    }
+    // m_run in RAW score units, exp2 arguments fma(s, c, -m c) with c = scale * log2(e) > 0.  The rescale of O is DO / 2 accumulator registers,
+    // through v_accvgpr moves
+    attn_lazy_max<false>(o, m_run, l_run, attn_tile_max(s), p.scale_log2);
     const float mc = m_run * p.scale_log2;
     float ps = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], p.scale_log2, -mc));
-      s[r] = e;
+      const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[0][r], p.scale_log2, -mc));
+      s[0][r] = e;
       ps += e;
     }
     l_run += ps;
-    // O^T += V^T * P^T: chunk c covers keys 16c + 8 hi + 0..7 = logical slot 2c + hi of the d row
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      V8 pf;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pf[j] = from_f32<T>(s[8 * c + j]);
-#pragma unroll
-      for (int t2 = 0; t2 < DT; ++t2) {
-        const V8 vf = *reinterpret_cast<const V8*>(sV + vofs[c] + t2 * 1024);
-        o[t2] = mfma32(vf, pf, o[t2]);
-      }
-    }
+    attn_pv<T, 1024>(o, s, sV, vofs);             // accumulator tile t2 = 32 d = 16 LDS rows of d pairs
   }
 
   if constexpr (SPLIT) {
@@ -263,7 +201,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void a
         for (int j = 0; j < 4; ++j) v[j] = o[t][4 * g + j];
         *reinterpret_cast<f32x4*>(wp + t * 32 + 8 * g + 4 * hi) = v;
       }
-    const float l = l_run + __shfl_xor(l_run, 32, 64);
+    const float l = attn_row_sum<false>(o, l_run, hi);
     if (hi == 0 && dbase == 0) {                  // the column parts of d = 512 hold the same (m, l): one of them stores
       f32x2 ml;
       ml[0] = m_run; ml[1] = l;
@@ -271,19 +209,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void a
     }
   } else {
     // ---------------- normalise and store: O^T regs -> out[b, q, h*D + dbase + d], 4 consecutive d per 8-byte store; rows >= n_q are not written
-    const float inv = 1.f / (l_run + __shfl_xor(l_run, 32, 64));
-    if (q_ok) {
-      T* op = reinterpret_cast<T*>(p.out) + (long)b * p.out_bs + qrow * p.out_ld + (long)h * D + dbase;
-#pragma unroll
-      for (int t = 0; t < DT; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          V4 v;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = from_f32<T>(o[t][4 * g + j] * inv);
-          *reinterpret_cast<V4*>(op + t * 32 + 8 * g + 4 * hi) = v;
-        }
-    }
+    attn_scale_acc(o, 1.f / attn_row_sum<false>(o, l_run, hi));
+    if (q_ok) attn_store(o, reinterpret_cast<T*>(p.out) + (long)b * p.out_bs + qrow * p.out_ld + (long)h * D + dbase, hi, DO);
   }
 }
 

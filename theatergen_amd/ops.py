@@ -479,13 +479,8 @@ def conv_up2(x, w_folded, batch, in_h, in_w, cin, bias=None, out=None):
     return out
 
 
-def attention(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale,
-              out, out_ld, out_bs, k1=None, k1_ld=0, k1_bs=0, vt1=None, vt1_ld=0, vt1_bs=0, len1=0, w1=0.0, causal=False, w1_dev=None,
-              mask=None):
-    """``w1_dev``: fp32 device tensor read by the kernel instead of the launch constant ``w1`` (graph-replayable IP scale): 1 element, or ``batch``
-    elements = one weight per batch item (tg_attention_ps).
-    ``mask``: additive score bias, fp32 [Bm, Hm, Qm, len0] with Bm in {1, batch}, Hm in {1, heads}, Qm in {1, n_q} (size-1 dims broadcast)."""
-    _need_cuda(q)
+def _attn_desc(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale, out, out_ld, out_bs):
+    """AttnDesc of one unmasked softmax segment: what ``attention``, ``attention_wide`` and ``attention_relpos`` have in common"""
     d = AttnDesc()
     d.dtype = _dt(q)
     d.batch, d.heads, d.head_dim, d.n_q = int(batch), int(heads), int(head_dim), int(n_q)
@@ -493,11 +488,23 @@ def attention(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch,
     d.k0, d.k0_ld, d.k0_bs = _ptr(k0), int(k0_ld), int(k0_bs)
     d.vt0, d.vt0_ld, d.vt0_bs = _ptr(vt0), int(vt0_ld), int(vt0_bs)
     d.len0 = int(len0)
+    d.scale = float(scale)
+    d.out, d.out_ld, d.out_bs = _ptr(out), int(out_ld), int(out_bs)
+    return d
+
+
+def attention(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale,
+              out, out_ld, out_bs, k1=None, k1_ld=0, k1_bs=0, vt1=None, vt1_ld=0, vt1_bs=0, len1=0, w1=0.0, causal=False, w1_dev=None,
+              mask=None):
+    """``w1_dev``: fp32 device tensor read by the kernel instead of the launch constant ``w1`` (graph-replayable IP scale): 1 element, or ``batch``
+    elements = one weight per batch item (tg_attention_ps).
+    ``mask``: additive score bias, fp32 [Bm, Hm, Qm, len0] with Bm in {1, batch}, Hm in {1, heads}, Qm in {1, n_q} (size-1 dims broadcast)."""
+    _need_cuda(q)
+    d = _attn_desc(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale, out, out_ld, out_bs)
     d.k1, d.k1_ld, d.k1_bs = _ptr(k1), int(k1_ld), int(k1_bs)
     d.vt1, d.vt1_ld, d.vt1_bs = _ptr(vt1), int(vt1_ld), int(vt1_bs)
     d.len1 = int(len1)
-    d.scale, d.w1 = float(scale), float(w1)
-    d.out, d.out_ld, d.out_bs = _ptr(out), int(out_ld), int(out_bs)
+    d.w1 = float(w1)
     d.causal = 1 if causal else 0
     n_w1 = 0
     if w1_dev is not None:
@@ -574,14 +581,7 @@ def attention_relpos(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, batch
         _need_cuda(t)
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
             raise RuntimeError(f"attention_relpos: bh / bw must be contiguous fp32 device tensors of {n} elements ([batch, heads, grid^2, grid])")
-    d = AttnDesc()
-    d.dtype = _dt(q)
-    d.batch, d.heads, d.head_dim, d.n_q, d.len0 = int(batch), int(heads), int(head_dim), int(grid) ** 2, int(grid) ** 2
-    d.q, d.q_ld, d.q_bs = _ptr(q), int(q_ld), int(q_bs)
-    d.k0, d.k0_ld, d.k0_bs = _ptr(k0), int(k0_ld), int(k0_bs)
-    d.vt0, d.vt0_ld, d.vt0_bs = _ptr(vt0), int(vt0_ld), int(vt0_bs)
-    d.scale = float(scale)
-    d.out, d.out_ld, d.out_bs = _ptr(out), int(out_ld), int(out_bs)
+    d = _attn_desc(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, int(grid) ** 2, batch, heads, head_dim, int(grid) ** 2, scale, out, out_ld, out_bs)
     _lib.check(_lib.lib().tg_attention_relpos(C.byref(d), _ptr(bh), _ptr(bw), int(grid), _stream()))
     return out
 
@@ -677,15 +677,7 @@ def attention_wide(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, b
     32-key tiles).  More than one effective split runs ``tg_attention_wide_split``: a partial launch and a combine launch, fp32 partials in the
     persistent ``workspace`` of the current slot (``tg_attention_wide_workspace_bytes``)."""
     _need_cuda(q)
-    d = AttnDesc()
-    d.dtype = _dt(q)
-    d.batch, d.heads, d.head_dim, d.n_q = int(batch), int(heads), int(head_dim), int(n_q)
-    d.q, d.q_ld, d.q_bs = _ptr(q), int(q_ld), int(q_bs)
-    d.k0, d.k0_ld, d.k0_bs = _ptr(k0), int(k0_ld), int(k0_bs)
-    d.vt0, d.vt0_ld, d.vt0_bs = _ptr(vt0), int(vt0_ld), int(vt0_bs)
-    d.len0 = int(len0)
-    d.scale = float(scale)
-    d.out, d.out_ld, d.out_bs = _ptr(out), int(out_ld), int(out_bs)
+    d = _attn_desc(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale, out, out_ld, out_bs)
     L = _lib.lib()
     S = 1
     if key_splits is not None and int(key_splits) != 1:

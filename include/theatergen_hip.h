@@ -314,6 +314,37 @@ int tg_relpos_tables(int32_t dtype, int32_t batch, int32_t heads, int32_t head_d
                      const void* rel_pos_h, const void* rel_pos_w, float* bh, float* bw, void* stream);
 int tg_attention_relpos(const tg_attn_desc* d, const float* bh, const float* bw, int32_t grid, void* stream);
 
+/* SWIN SHIFTED-WINDOW ATTENTION on image-ordered tokens (csrc/tg_attention_swin.hip), for GroundingDINO's Swin backbone (the reference's `detect`,
+ * utils/detector.py).  It restates transformers.models.swin.modeling_swin.SwinLayer.forward between layernorm_before and the output projection, window 7;
+ * the pad, roll, window partition, learned bias, shift mask, un-partition, un-roll and crop are address arithmetic: nothing but q, k, v, the pad vectors and
+ * the table is read, nothing but out is written, and no [windows, 49, 49] tensor exists.
+ *   q, k, v   x[b, r*W + c, h*32 + ch] in the model dtype, row pitch *_ld and batch pitch *_bs in elements (normally three column slices of one
+ *             [batch*H*W, 3C] projection output); out the same layout, written for the H*W real tokens only.
+ *   pad_q, pad_k, pad_v   [heads*32], model dtype: q / k / v of a padded token (transformers pads zeros after the LayerNorm: the projection biases).
+ *   table     [169, heads], model dtype: the layer's relative_position_bias_table.
+ * With Hp = ceil(H/7)*7, Wp = ceil(W/7)*7: position (r, c) of the padded, rolled map holds source ((r + shift) mod Hp, (c + shift) mod Wp); a source with
+ * row >= H or column >= W is a padded token (a real key of its window, never masked, its own output never stored).  The window of (r, c) is (r/7, c/7),
+ * tokens row-major inside it.  For query i and key j of one window
+ *     score = scale * q_i.k_j + table[(ri - rj + 6)*13 + (ci - cj + 6), h] + m_ij
+ * where m_ij = -100 (finite, as transformers has it) if shift > 0 and region(i) != region(j), else 0, with
+ *     region = 3*((r >= Hp-7) + (r >= Hp-shift)) + ((c >= Wp-7) + (c >= Wp-shift))        on rolled coordinates.
+ * Scores are accumulated in fp32 from the stored operands; scale, bias and mask are applied in fp32; the softmax runs over the 49 keys in fp32; P is
+ * rounded to the storage dtype where it enters PV; O is accumulated in fp32, rounded once and stored at the query's SOURCE position.  Every output element
+ * is written by exactly one lane, no atomics, no workspace: equal inputs give equal bits, and a batch item's rows do not depend on the batch.
+ * Instances: head_dim 32, window 7, bf16 and fp16; one wave per (batch item, window, head), four per workgroup, no scratch.  Everything else is refused on
+ * the host before any launch, writing nothing, with tg_last_error() set:
+ *   TG_ERR_UNSUPPORTED  another head_dim or window (Swin-B's 12).
+ *   TG_ERR_ARG          a null pointer; bad dtype; batch or heads < 1; H < 7 or W < 7 (not supported: transformers' backbone would pad such a grid to one
+ *                       window); a side > 32768; shift not in {0, 3}; scale <= 0; q_ld / k_ld / v_ld not multiples of 8 or out_ld not a multiple of 4, or
+ *                       any of them < heads*32, with batch > 1 the same multiples for the batch pitches, a negative input batch pitch, or out_bs that
+ *                       does not clear one item's H*W rows (outputs of two items would overlap); q, k, v or a pad vector not 16-byte aligned, out
+ *                       not 8-byte aligned.
+ * Additive to ABI 308: one new symbol, no descriptor, TG_ABI_VERSION unchanged. */
+int tg_attention_swin(int32_t dtype, int32_t batch, int32_t heads, int32_t head_dim, int32_t window, int32_t H, int32_t W, int32_t shift, float scale,
+                      const void* q, int64_t q_ld, int64_t q_bs, const void* k, int64_t k_ld, int64_t k_bs, const void* v, int64_t v_ld, int64_t v_bs,
+                      const void* pad_q, const void* pad_k, const void* pad_v, const void* table, void* out, int64_t out_ld, int64_t out_bs,
+                      void* stream);
+
 /* Reverse pass of SELF-attention without materialised probabilities (round 5, ABI 306; csrc/tg_attention_bwd.hip), head_dim <= 64, n % 8 == 0:
  *     dQ = dS K,  dK = dS^T Q,  dV = P^T dO   with  P = softmax(scale Q K^T),  dS = scale P o (dO V^T - rowsum(P o dO V^T))
  * — what `torch.autograd.grad(loss, latents)` of the guidance step (models/pipelines.py:62-128) computes through `Attention` / AttnProcessor

@@ -145,6 +145,7 @@ SIGNATURES = {
     "tg_attention_wide_split": (i32, [C.POINTER(AttnDesc), i32, vp, i64, vp]),
     "tg_relpos_tables": (i32, [i32, i32, i32, i32, i32, vp, i64, i64, vp, vp, vp, vp, vp]),
     "tg_attention_relpos": (i32, [C.POINTER(AttnDesc), vp, vp, i32, vp]),
+    "tg_attention_swin": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, i64, vp]),
     "tg_sam_posenc": (i32, [i32, vp, i64, vp, i32, vp, vp, vp, vp]),
     "tg_sam_mask_head": (i32, [i32, vp, i32, i32, vp, vp, vp, vp, i32, f32, vp, vp]),
     "tg_sam_mask_post": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp, vp]),

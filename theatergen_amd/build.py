@@ -136,6 +136,9 @@ HOT_GATES = [
     # SAM's rel-pos attention (tg_attention_relpos.hip, template <T, DPAD, DV, ONES, G>): two waves per SIMD; the bias lives in registers (32 Bw values at
     # G = 64, 14 + 14 table entries at G = 14 with the tile loop unrolled) — scratch would mean one of those arrays was indexed at run time
     ("attention_relpos_kernel<", 0, 256),
+    # Swin window attention (tg_attention_swin.hip, template <T>): one wave per (window, head); 16 K-fragment, 32 score and 16 output registers with compile-time
+    # indices (scratch = one of them, or the key-offset constants of the bias lookup, was indexed at run time).  128 VGPRs keeps four waves per SIMD
+    ("attention_swin_kernel<", 0, 128),
     # SAM's prompt / mask head (tg_sam_head.hip).  The mask head keeps two GEMMs' accumulators, the LayerNorm and the second GEMM's B operand in registers
     # with compile-time indices (scratch = one of those arrays was indexed at run time); the positional encoding calls the precise sinf / cosf on a reduced
     # argument (scratch = the large-argument path's tables came back); the post-processing is scalar code

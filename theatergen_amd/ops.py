@@ -586,6 +586,42 @@ def attention_relpos(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, batch
     return out
 
 
+def attention_swin(q, q_ld, q_bs, k, k_ld, k_bs, v, v_ld, v_bs, pad_q, pad_k, pad_v, table, batch, heads, H, W, shift, scale, out, out_ld, out_bs,
+                   head_dim=32, window=7):
+    """``tg_attention_swin``: Swin window attention on image-ordered tokens ``x[b, r * W + c, h * 32 + ch]`` (pitches in elements): pad to a multiple of
+    7, roll by ``-shift``, 7 x 7 windows, the learned bias ``table`` [169, heads], the shift mask and their inverses are address arithmetic inside the
+    kernel.  ``pad_q`` / ``pad_k`` / ``pad_v`` [heads * 32]: q / k / v of a padded token (the projection biases).  Writes the H * W real tokens of ``out``."""
+    _need_cuda(q)
+    hd = int(heads) * int(head_dim)
+    for name, t in (("pad_q", pad_q), ("pad_k", pad_k), ("pad_v", pad_v)):
+        _need_cuda(t)
+        if t.dtype != q.dtype or t.numel() != hd or not t.is_contiguous():
+            raise RuntimeError(f"attention_swin: {name} must be a contiguous {q.dtype} device tensor of {hd} elements, got {tuple(t.shape)} {t.dtype}")
+    n, batch = int(H) * int(W), int(batch)
+    for name, t, ld, bs in (("q", q, q_ld, q_bs), ("k", k, k_ld, k_bs), ("v", v, v_ld, v_bs), ("out", out, out_ld, out_bs)):
+        _need_cuda(t)
+        if t.dtype != q.dtype or t.device != q.device:
+            raise RuntimeError(f"attention_swin: {name} must be a {q.dtype} tensor on {q.device}, got {t.dtype} on {t.device}")
+        if t.stride(-1) != 1:
+            raise RuntimeError(f"attention_swin: {name} must have unit stride along the channels")
+        if int(ld) < hd or int(bs) < 0 or (name == "out" and batch > 1 and int(bs) < (n - 1) * int(ld) + hd):
+            raise RuntimeError(f"attention_swin: {name} pitches (row {ld}, batch {bs}) do not hold {n} rows of {hd} channels per batch item without overlap")
+        # the last element the kernel touches must lie inside the tensor's storage (the C entry point cannot know buffer sizes)
+        need = (batch - 1) * int(bs) + (n - 1) * int(ld) + hd
+        have = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+        if n < 1 or batch < 1 or have < need:
+            raise RuntimeError(f"attention_swin: {name} holds {have} elements from its first, {need} are addressed (batch {batch}, {H} x {W} tokens, "
+                               f"row pitch {ld}, batch pitch {bs})")
+    _need_cuda(table)
+    if table.dtype != q.dtype or not table.is_contiguous() or tuple(table.shape) != ((2 * int(window) - 1) ** 2, int(heads)):
+        raise RuntimeError(f"attention_swin: table must be a contiguous {q.dtype} device tensor [{(2 * int(window) - 1) ** 2}, {int(heads)}], "
+                           f"got {tuple(table.shape)} {table.dtype}")
+    _lib.check(_lib.lib().tg_attention_swin(_dt(q), int(batch), int(heads), int(head_dim), int(window), int(H), int(W), int(shift), float(scale),
+                                            _ptr(q), int(q_ld), int(q_bs), _ptr(k), int(k_ld), int(k_bs), _ptr(v), int(v_ld), int(v_bs),
+                                            _ptr(pad_q), _ptr(pad_k), _ptr(pad_v), _ptr(table), _ptr(out), int(out_ld), int(out_bs), _stream()))
+    return out
+
+
 def _f32_dev(t, what, numel=None):
     _need_cuda(t)
     if t.dtype != torch.float32 or not t.is_contiguous() or (numel is not None and t.numel() != numel):

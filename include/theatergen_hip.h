@@ -283,6 +283,27 @@ int tg_attention_wide_splits(const tg_attn_desc* d, int32_t requested);
 int64_t tg_attention_wide_workspace_bytes(const tg_attn_desc* d, int32_t splits);
 int tg_attention_wide_split(const tg_attn_desc* d, int32_t splits, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* tg_attention_wide with a KEY-PADDING MASK, for GroundingDINO's bidirectional fusion attention (transformers' GroundingDinoBiMultiHeadAttention: 4 heads
+ * of dim 256, text keys / vision keys with padding).  tg_attention_wide and tg_attention_wide_split keep refusing any mask; this entry runs the same
+ * kernel bodies with a KMASK template flag (kernels of their own names: the unmasked instances keep theirs):
+ *     O[b,h,i,:] = softmax_j( scale * q_i.k_j + (key_mask[b*key_mask_bs + j] ? -inf : 0) ) V
+ *   key_mask   uint8 [batch][len0], 1 = the key is masked for every query and head of its batch item; 8-byte aligned, batch pitch key_mask_bs (bytes) a
+ *              multiple of 8 and >= len0.  It is read with one 8-byte load per run of 8 keys.
+ *   splits     >= 1, as tg_attention_wide_split: min(splits, nt) effective splits; 1 runs the unsplit kernel and touches no workspace, more run the
+ *              partial and the combine launch with the workspace layout and size of tg_attention_wide_workspace_bytes.
+ * A masked key's score is -inf where a key >= len0 already gets it, so it contributes exactly 0 to the max, the sum and PV.  A whole 32-key tile, or a
+ * whole split, may be masked: while no unmasked key has been seen the running max is -inf and probabilities are formed against the reference 0
+ * (exp2(-inf) = 0 exactly, never exp2(-inf + inf)); such a split hands the combine (m, l, o) = (-inf, 0, 0) and is given the weight 0 there.  A row whose
+ * keys are ALL masked is outside the contract: transformers gives NaN, this entry writes zeros.
+ * len0 still has to be a multiple of 8, but the mask frees callers from it: pad len0 and the V^T pitch to a multiple of 8 and mask the tail (K rows of
+ * the tail are read and must be addressable; V^T columns of the tail are multiplied by P = 0 and must be finite).
+ * An all-zero mask gives the bits of tg_attention_wide / tg_attention_wide_split for the same splits.  Deterministic, batch-independent, no atomics.
+ * Errors: every check of tg_attention_wide, then TG_ERR_ARG for a null or misaligned key_mask, a bad key_mask_bs (batch > 1), splits < 1, or a
+ * missing / misaligned / short workspace when min(splits, nt) > 1; all before any launch, a refused call writes nothing.
+ * Additive to ABI 308: one new symbol, tg_attn_desc unchanged, TG_ABI_VERSION unchanged. */
+int tg_attention_wide_kmask(const tg_attn_desc* d, const uint8_t* key_mask, int64_t key_mask_bs, int32_t splits, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
 /* Self-attention with SAM's DECOMPOSED RELATIVE-POSITION BIAS (csrc/tg_attention_relpos.hip; transformers' SamVisionAttention.get_decomposed_rel_pos),
  * for the Segment-Anything image encoder that runs between the two stages (reference models/sam.py).  A batch item is one square grid of side `grid`:
  * an image (grid 64) or one 14 x 14 window (grid 14); its N = grid^2 tokens are row-major, token i = (qh, qw) = (i / grid, i % grid).
@@ -344,6 +365,38 @@ int tg_attention_swin(int32_t dtype, int32_t batch, int32_t heads, int32_t head_
                       const void* q, int64_t q_ld, int64_t q_bs, const void* k, int64_t k_ld, int64_t k_bs, const void* v, int64_t v_ld, int64_t v_bs,
                       const void* pad_q, const void* pad_k, const void* pad_v, const void* table, void* out, int64_t out_ld, int64_t out_bs,
                       void* stream);
+
+/* MULTI-SCALE DEFORMABLE ATTENTION from the projected operands on (csrc/tg_msdeform_attn.hip), for GroundingDINO's deformable encoder (and, with
+ * ref_dim 4, its decoder).  It restates transformers' GroundingDinoMultiscaleDeformableAttention between its projections: where that module runs L
+ * grid_sample calls, a stack, a multiply and a sum over a [batch*heads, 32, n_q, L*4] fp32 tensor, this is a gather of L*4*4 taps of 64 contiguous bytes
+ * per (query, head); nothing but the operands is read and nothing but out is written.
+ *   shapes      HOST int32 [n_levels][2] = (H_l, W_l), read during the call.  The tokens of the levels are concatenated: level l starts at
+ *               sum_{k<l} H_k W_k, Nv = the sum over all levels.
+ *   value       [batch][Nv][heads*32], model dtype, row pitch v_ld and batch pitch v_bs (elements).
+ *   offsets     row b*n_q + q holds [heads][L][4][2] = (x, y) offsets, model dtype, row pitch off_ld.
+ *   logits      row b*n_q + q holds [heads][L*4], model dtype, row pitch log_ld.  Offsets and logits are normally two column slices of one GEMM output.
+ *   ref         fp32, dense [batch][n_q][L][ref_dim]: (x, y) in [0, 1] of the level (ref_dim 2) or (x, y, w, h) boxes (ref_dim 4).
+ *   value_mask  optional uint8, dense [batch][Nv], 1 = padding token; NULL = none.
+ *   out         [batch][n_q][heads*32], model dtype, row pitch out_ld, batch pitch out_bs.
+ * In fp32 from the stored operands: w = softmax over the L*4 logits of a (query, head); the pixel position of sample (l, p), with grid_sample's
+ * align_corners = False,
+ *     ref_dim 2:  x = ref_x * W_l + off_x - 0.5                      y = ref_y * H_l + off_y - 0.5          (the offset normaliser (W_l, H_l) cancels)
+ *     ref_dim 4:  x = (ref_x + off_x / 4 * ref_w * 0.5) * W_l - 0.5   y likewise with ref_h, H_l
+ * bilinear interpolation over the four neighbours (floor(x) + {0, 1}, floor(y) + {0, 1}); a neighbour outside the map contributes 0 and so does one on
+ * a token with value_mask = 1 (this replaces transformers' masked_fill on `value`: there is no pass over value); a NaN or huge position samples nothing.
+ *     out[b, q, h*32 + c] = sum_{l, p} w[l*4 + p] * sample_{l,p}[c]          fp32 accumulation, rounded once.
+ * Every output element is written by exactly one lane, no atomics, no workspace: equal inputs give equal bits, and a batch item's rows do not depend on the
+ * batch.  Instances: head_dim 32, n_points 4, 1 <= n_levels <= 4, ref_dim 2 / 4, with / without mask, bf16 and fp16; a group of 4 lanes per (query, head),
+ * no LDS, no scratch.  n_q need not equal Nv.  Everything else is refused on the host before any launch, writing nothing, with tg_last_error() set:
+ *   TG_ERR_UNSUPPORTED  another head_dim, n_points, n_levels or ref_dim.
+ *   TG_ERR_ARG          bad dtype; batch, heads or n_q < 1; a null pointer (value_mask excepted); a level side < 1 or > 32768, or 2^31 or more tokens;
+ *                       v_ld / out_ld not multiples of 8 or < heads*32; off_ld not a multiple of 8 or < heads*L*8; log_ld not a multiple of 4 or
+ *                       < heads*L*4; with batch > 1 v_bs / out_bs not multiples of 8, v_bs < 0, or out_bs that does not clear one item's n_q rows;
+ *                       value, offsets, ref or out not 16-byte aligned, logits not 8-byte aligned.
+ * Additive to ABI 308: one new symbol, no descriptor, TG_ABI_VERSION unchanged. */
+int tg_msdeform_attn(int32_t dtype, int32_t batch, int32_t heads, int32_t head_dim, int32_t n_levels, int32_t n_points, int32_t n_q, int32_t ref_dim,
+                     const int32_t* shapes, const void* value, int64_t v_ld, int64_t v_bs, const void* offsets, int64_t off_ld, const void* logits,
+                     int64_t log_ld, const float* ref, const uint8_t* value_mask, void* out, int64_t out_ld, int64_t out_bs, void* stream);
 
 /* Reverse pass of SELF-attention without materialised probabilities (round 5, ABI 306; csrc/tg_attention_bwd.hip), head_dim <= 64, n % 8 == 0:
  *     dQ = dS K,  dK = dS^T Q,  dV = P^T dO   with  P = softmax(scale Q K^T),  dS = scale P o (dO V^T - rowsum(P o dO V^T))
@@ -423,6 +476,19 @@ int tg_layernorm(int32_t dtype, const void* x, int64_t rows, int32_t C, int64_t 
 /* Row statistics of tg_layernorm only: stats[m] = (rstd, -rstd * mean) fp32 [rows][2] (two-pass mean / centred biased variance over the
  * stored values) — the `ln_rows` input of the LayerNorm-folded projections (tg_gemm_desc.ln_u): half the traffic of the normalising pass. */
 int tg_layernorm_stats(int32_t dtype, const void* x, int64_t rows, int32_t C, int64_t ldx, float eps, float* stats, void* stream);
+
+/* LayerNorm of a SUM (csrc/tg_layernorm_add.hip), for post-norm residual blocks (GroundingDINO's encoder: hidden = LN(hidden + sublayer(hidden))):
+ *     out[row, :] = LN(x[row, :] + res[row, :]) * gamma + beta
+ * x, res and out are [rows][C] in the model dtype with row pitches ldx, ldres, ldo (elements); gamma, beta [C] in the model dtype.  Both operands are
+ * read in the storage dtype, ADDED IN FP32, and mean / centred variance (two passes, fp32, in registers) are taken from that sum, so the result is
+ * rounded once; a GEMM with a residual epilogue followed by tg_layernorm rounds the sum to the storage dtype first.  out may alias x or res (a row is
+ * read completely before it is written, by the lanes that write it).  Deterministic, no workspace, no atomics.
+ *   TG_ERR_UNSUPPORTED  C > 1280.
+ *   TG_ERR_ARG          bad dtype; a null pointer; rows < 1; C < 8 or not a multiple of 8; a row pitch that is no multiple of 8 or is below C; a pointer
+ *                       that is not 16-byte aligned.
+ * Additive to ABI 308: one new symbol, TG_ABI_VERSION unchanged. */
+int tg_layernorm_add(int32_t dtype, const void* x, int64_t ldx, const void* res, int64_t ldres, int64_t rows, int32_t C, float eps, const void* gamma,
+                     const void* beta, void* out, int64_t ldo, void* stream);
 /* GroupNorm statistics only: coef[b][0][c] = rstd(b, group(c)) * gamma[c], coef[b][1][c] = beta[c] - mean(b, group(c)) * coef[b][0][c]
  * (fp32 [batch][2][c0 + c1]; the same reductions, in the same order, as tg_groupnorm) for tg_gemm_desc.a_coef: the apply pass
  * (normalise + SiLU, one HBM write + read of the activation per conv) moves into the consumer conv's window staging. */

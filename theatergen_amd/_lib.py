@@ -143,6 +143,8 @@ SIGNATURES = {
     "tg_attention_wide_splits": (i32, [C.POINTER(AttnDesc), i32]),
     "tg_attention_wide_workspace_bytes": (i64, [C.POINTER(AttnDesc), i32]),
     "tg_attention_wide_split": (i32, [C.POINTER(AttnDesc), i32, vp, i64, vp]),
+    "tg_attention_wide_kmask": (i32, [C.POINTER(AttnDesc), vp, i64, i32, vp, i64, vp]),
+    "tg_msdeform_attn": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i64, i64, vp]),
     "tg_relpos_tables": (i32, [i32, i32, i32, i32, i32, vp, i64, i64, vp, vp, vp, vp, vp]),
     "tg_attention_relpos": (i32, [C.POINTER(AttnDesc), vp, vp, i32, vp]),
     "tg_attention_swin": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, i64, vp]),
@@ -157,6 +159,7 @@ SIGNATURES = {
     "tg_groupnorm_scratch_bytes": (i64, [i32, i64, i32]),
     "tg_groupnorm": (i32, [i32, vp, vp, i32, i32, i32, i64, i32, f32, vp, vp, i32, vp, vp, vp]),
     "tg_layernorm": (i32, [i32, vp, i64, i32, i64, f32, vp, vp, vp, i64, vp]),
+    "tg_layernorm_add": (i32, [i32, vp, i64, vp, i64, i64, i32, f32, vp, vp, vp, i64, vp]),
     "tg_layernorm_stats": (i32, [i32, vp, i64, i32, i64, f32, vp, vp]),
     "tg_groupnorm_coef": (i32, [i32, vp, vp, i32, i32, i32, i64, i32, f32, vp, vp, vp, vp, vp]),
     "tg_groupnorm_from_partials": (i32, [i32, vp, i32, i32, i64, i32, f32, vp, vp, i32, vp, vp, vp, i32, vp]),

@@ -139,6 +139,10 @@ HOT_GATES = [
     # Swin window attention (tg_attention_swin.hip, template <T>): one wave per (window, head); 16 K-fragment, 32 score and 16 output registers with compile-time
     # indices (scratch = one of them, or the key-offset constants of the bias lookup, was indexed at run time).  128 VGPRs keeps four waves per SIMD
     ("attention_swin_kernel<", 0, 128),
+    # multi-scale deformable attention (tg_msdeform_attn.hip, template <T, R, MASK>): a gather, latency-bound.  The 16 taps of a level (16 registers of
+    # 16-byte loads x 4) are in flight together next to 16 softmax weights, 16 tap weights and 8 accumulators, all with compile-time indices (scratch = one
+    # of those arrays was indexed at run time).  128 VGPRs (what the masked instances take; 120 - 126 without mask) keeps four waves per SIMD
+    ("msdeform_attn_kernel<", 0, 128),
     # SAM's prompt / mask head (tg_sam_head.hip).  The mask head keeps two GEMMs' accumulators, the LayerNorm and the second GEMM's B operand in registers
     # with compile-time indices (scratch = one of those arrays was indexed at run time); the positional encoding calls the precise sinf / cosf on a reduced
     # argument (scratch = the large-argument path's tables came back); the post-processing is scalar code
@@ -146,6 +150,10 @@ HOT_GATES = [
     ("sam_posenc_kernel<", 0, 64),
     ("sam_mask_post_kernel", 0, 96),
     ("attention_wide_combine_kernel<", 0, 64),
+    # the key-padding-mask instances of the two kernels around this entry (tg_attention_wide_kmask; <T, D, DO, SPLIT> / <T, D>): the same bodies with a KMASK flag, kernels of
+    # their own names so that the unmasked instances keep theirs; the same budgets for the same reasons (the mask is two 8-byte loads per lane and tile)
+    ("attention_wide_combine_kmask_kernel<", 0, 64),
+    ("attention_wide_kmask_kernel<", 0, 256),
     ("attention_wide_kernel<", 0, 256),
     ("gemm_glds_kernel<", 0, 256),                                 # the LDS-DMA GEMM family: no scratch anywhere
     ("conv_halo_kernel<", 0, 256),

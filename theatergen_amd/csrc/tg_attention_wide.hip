@@ -52,6 +52,8 @@ struct WideParams {
   // key split only (appended: the unsplit instances read nothing past out_bs)
   int batch, splits;
   float* ws;
+  // key-padding mask only (KMASK instances): uint8 [batch][len], 1 = masked, batch pitch kmask_bs
+  const unsigned char* kmask; long kmask_bs;
 };
 
 struct CombineParams {
@@ -62,8 +64,9 @@ struct CombineParams {
   void* out; long out_ld, out_bs;
 };
 
-template <typename T, int D, int DO, bool SPLIT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void attention_wide_kernel(WideParams p) {
+// the body of attention_wide_kernel (KMASK = false: the kernel as it always was) and attention_wide_kmask_kernel (KMASK = true)
+template <typename T, int D, int DO, bool SPLIT, bool KMASK>
+__device__ __forceinline__ void attention_wide_body(WideParams p) {
   typedef __attribute__((ext_vector_type(2))) float f32x2;
   typedef typename Vec<T>::v8 V8;
   constexpr int NP = D / 64;                    // K panels
@@ -171,10 +174,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void a
       for (int r = 0; r < 16; ++r)
         if (kv0 + 16 * (r >> 3) + 8 * hi + (r & 7) >= p.len) s[0][r] = -INFINITY;
     }
+    if constexpr (KMASK) {
+      // the lane's 16 keys are two runs of 8: one 8-byte load of mask bytes each (len % 8 == 0: a run is inside len or wholly past it, where the
+      // block above has already set -inf and nothing is read)
+      const unsigned char* mp = p.kmask + (long)b * p.kmask_bs + kv0 + 8 * hi;
+#pragma unroll
+      for (int cc = 0; cc < 2; ++cc) {
+        if (kv0 + 16 * cc + 8 * hi < p.len) {
+          const unsigned long long mw = *reinterpret_cast<const unsigned long long*>(mp + 16 * cc);
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if ((mw >> (8 * j)) & 0xff) s[0][8 * cc + j] = -INFINITY;
+        }
+      }
+    }
     // m_run in RAW score units, exp2 arguments fma(s, c, -m c) with c = scale * log2(e) > 0.  The rescale of O is DO / 2 accumulator registers,
     // through v_accvgpr moves
     attn_lazy_max<false>(o, m_run, l_run, attn_tile_max(s), p.scale_log2);
-    const float mc = m_run * p.scale_log2;
+    // KMASK: while every key so far was masked m_run is still -inf and fma(-inf, c, +inf) would be NaN; against the reference 0 such a tile's
+    // probabilities are exp2(-inf) = 0 exactly, and the first finite tile rescales the (zero) accumulators by exp2(-inf) = 0
+    const float mc = (KMASK && m_run == -INFINITY) ? 0.f : m_run * p.scale_log2;
     float ps = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -209,15 +228,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void a
     }
   } else {
     // ---------------- normalise and store: O^T regs -> out[b, q, h*D + dbase + d], 4 consecutive d per 8-byte store; rows >= n_q are not written
-    attn_scale_acc(o, 1.f / attn_row_sum<false>(o, l_run, hi));
+    const float l = attn_row_sum<false>(o, l_run, hi);
+    attn_scale_acc(o, (KMASK && !(l > 0.f)) ? 0.f : 1.f / l);      // a row with every key masked is outside the contract: zeros, not NaN
     if (q_ok) attn_store(o, reinterpret_cast<T*>(p.out) + (long)b * p.out_bs + qrow * p.out_ld + (long)h * D + dbase, hi, DO);
   }
 }
 
+template <typename T, int D, int DO, bool SPLIT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void attention_wide_kernel(WideParams p) {
+  attention_wide_body<T, D, DO, SPLIT, false>(p);
+}
+
+// KMASK: the same loop with a key-padding mask (tg_attention_wide_kmask).  A kernel of its own name: the instances above keep theirs
+template <typename T, int D, int DO, bool SPLIT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void attention_wide_kmask_kernel(WideParams p) {
+  attention_wide_body<T, D, DO, SPLIT, true>(p);
+}
+
 // Combine of the key-split partials: one thread per 4 consecutive output columns of one (batch, head, query < n_q); 16-byte loads of o, 8-byte stores of out
 // (exactly the elements the unsplit kernel writes).  fp32 throughout, s ascending (deterministic), one rounding.
-template <typename T, int D>
-__global__ __launch_bounds__(256) void attention_wide_combine_kernel(CombineParams p) {
+template <typename T, int D, bool KMASK>
+__device__ __forceinline__ void attention_wide_combine_body(CombineParams p) {
   typedef typename Vec<T>::v4 V4;
   typedef __attribute__((ext_vector_type(2))) float f32x2;
   constexpr int TPR = D / 4, RPB = 256 / TPR;    // threads per row, rows per block
@@ -241,22 +272,33 @@ __global__ __launch_bounds__(256) void attention_wide_combine_kernel(CombinePara
   for (int s = 0; s < p.splits; ++s) {
     const long r = r0 + s * sstride;
     const f32x2 ml = *reinterpret_cast<const f32x2*>(wml + r * 2);
-    const float w = __builtin_amdgcn_exp2f((ml[0] - M) * p.scale_log2);          // 1 for the split that holds the max, exactly 0 far below it
+    float w = __builtin_amdgcn_exp2f((ml[0] - M) * p.scale_log2);                // 1 for the split that holds the max, exactly 0 far below it
+    if (KMASK && ml[0] == -INFINITY) w = 0.f;                                    // a split whose keys are all masked (m = -inf, l = 0, o = 0); -inf - -inf is NaN
     const f32x4 v = *reinterpret_cast<const f32x4*>(wo + r * D + c);
     den = __builtin_fmaf(w, ml[1], den);
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[j] = __builtin_fmaf(w, v[j], acc[j]);
   }
-  const float inv = 1.f / den;
+  const float inv = (KMASK && !(den > 0.f)) ? 0.f : 1.f / den;                 // every key of the row masked: zeros (outside the contract)
   V4 o;
 #pragma unroll
   for (int j = 0; j < 4; ++j) o[j] = from_f32<T>(acc[j] * inv);
   *reinterpret_cast<V4*>(reinterpret_cast<T*>(p.out) + (long)b * p.out_bs + (long)q * p.out_ld + (long)h * D + c) = o;
 }
 
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attention_wide_combine_kernel(CombineParams p) {
+  attention_wide_combine_body<T, D, false>(p);
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attention_wide_combine_kmask_kernel(CombineParams p) {
+  attention_wide_combine_body<T, D, true>(p);
+}
+
 // S = 1: the unsplit kernel, no workspace.  S > 1: the partial launch (grid x S) and the combine launch, in this order on `st`
-template <typename T, int D, int DO, bool SPLIT>
-int launch_wide(const tg_attn_desc* d, hipStream_t st, int S, float* ws, const char* who) {
+template <typename T, int D, int DO, bool SPLIT, bool KMASK = false>
+int launch_wide(const tg_attn_desc* d, hipStream_t st, int S, float* ws, const char* who, const unsigned char* kmask = nullptr, long kmask_bs = 0) {
   WideParams p{};
   p.heads = d->heads; p.n_q = d->n_q; p.n_qblk = (d->n_q + 127) / 128;
   p.q = d->q; p.q_ld = d->q_ld; p.q_bs = d->q_bs;
@@ -266,15 +308,16 @@ int launch_wide(const tg_attn_desc* d, hipStream_t st, int S, float* ws, const c
   p.scale_log2 = d->scale * 1.4426950408889634f;
   p.out = d->out; p.out_ld = d->out_ld; p.out_bs = d->out_bs;
   p.batch = d->batch; p.splits = S; p.ws = ws;
+  p.kmask = kmask; p.kmask_bs = kmask_bs;
   const size_t lds = (size_t)2 * ((D / 64) * 32 * 64 + DO * 32) * sizeof(T);
   const long blocks = (long)p.n_qblk * d->heads * d->batch * (D / DO) * S;
   TG_CHECK(blocks <= 0x7fffffffL, TG_ERR_ARG, "%s: problem too large for one launch", who);
   constexpr int RPB = 256 / (D / 4);
   const long total = (long)d->batch * d->heads * d->n_q, cblocks = (total + RPB - 1) / RPB;
   TG_CHECK(cblocks <= 0x7fffffffL, TG_ERR_ARG, "%s: problem too large for one launch", who);
-  auto k = attention_wide_kernel<T, D, DO, SPLIT>;
+  auto k = KMASK ? attention_wide_kmask_kernel<T, D, DO, SPLIT> : attention_wide_kernel<T, D, DO, SPLIT>;
   // the dynamic LDS of a stage pair (96 KiB at d = 512) is above the default limit: raised once per device, and a refusal is this call's error
-  static bool raised[64] = {};       // no lock: two threads that race here only repeat the same idempotent attribute call
+  static bool raised[64] = {};       // one table per instantiation of launch_wide, KMASK included; no lock: two threads that race here only repeat the same idempotent attribute call
   int dev = 0;
   TG_CHECK(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, TG_ERR_LAUNCH, "%s: no current device", who);
   if (!raised[dev]) {
@@ -291,15 +334,21 @@ int launch_wide(const tg_attn_desc* d, hipStream_t st, int S, float* ws, const c
     c.ws = ws;
     c.scale_log2 = p.scale_log2;
     c.out = d->out; c.out_ld = d->out_ld; c.out_bs = d->out_bs;
-    hipLaunchKernelGGL((attention_wide_combine_kernel<T, D>), dim3((unsigned)cblocks), dim3(256), 0, st, c);
+    if constexpr (KMASK) hipLaunchKernelGGL((attention_wide_combine_kmask_kernel<T, D>), dim3((unsigned)cblocks), dim3(256), 0, st, c);
+    else hipLaunchKernelGGL((attention_wide_combine_kernel<T, D>), dim3((unsigned)cblocks), dim3(256), 0, st, c);
     TG_LAUNCH_CHECK();
   }
   return TG_OK;
 }
 
 template <bool SPLIT>
-int dispatch_wide(const tg_attn_desc* d, hipStream_t st, int S, float* ws, const char* who) {
+int dispatch_wide(const tg_attn_desc* d, hipStream_t st, int S, float* ws, const char* who, const unsigned char* kmask = nullptr, long kmask_bs = 0) {
   const bool bf = d->dtype == TG_BF16;
+  if (kmask) {
+    if (d->head_dim == 256)
+      return bf ? launch_wide<bf16_t, 256, 256, SPLIT, true>(d, st, S, ws, who, kmask, kmask_bs) : launch_wide<f16_t, 256, 256, SPLIT, true>(d, st, S, ws, who, kmask, kmask_bs);
+    return bf ? launch_wide<bf16_t, 512, 256, SPLIT, true>(d, st, S, ws, who, kmask, kmask_bs) : launch_wide<f16_t, 512, 256, SPLIT, true>(d, st, S, ws, who, kmask, kmask_bs);
+  }
   if (d->head_dim == 256) return bf ? launch_wide<bf16_t, 256, 256, SPLIT>(d, st, S, ws, who) : launch_wide<f16_t, 256, 256, SPLIT>(d, st, S, ws, who);
   return bf ? launch_wide<bf16_t, 512, 256, SPLIT>(d, st, S, ws, who) : launch_wide<f16_t, 512, 256, SPLIT>(d, st, S, ws, who);
 }
@@ -388,4 +437,22 @@ extern "C" int tg_attention_wide_split(const tg_attn_desc* d, int32_t splits, vo
   const long need = wide_ws_bytes(d, S);
   TG_CHECK(workspace_bytes >= need, TG_ERR_ARG, "tg_attention_wide_split: workspace of %lld bytes, %d splits need %ld", (long long)workspace_bytes, (int)S, need);
   return dispatch_wide<true>(d, st, (int)S, static_cast<float*>(workspace), "tg_attention_wide_split");
+}
+
+extern "C" int tg_attention_wide_kmask(const tg_attn_desc* d, const uint8_t* key_mask, int64_t key_mask_bs, int32_t splits, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+  const char* who = "tg_attention_wide_kmask";
+  const int rc = validate_wide(d, who);
+  if (rc != TG_OK) return rc;
+  TG_CHECK(key_mask != nullptr && (reinterpret_cast<uintptr_t>(key_mask) & 7) == 0, TG_ERR_ARG, "%s: key_mask must be non-null and 8-byte aligned", who);
+  TG_CHECK(d->batch == 1 || (key_mask_bs >= d->len0 && key_mask_bs % 8 == 0), TG_ERR_ARG,
+           "%s: key_mask_bs (%lld) must cover len0 and be a multiple of 8", who, (long long)key_mask_bs);
+  TG_CHECK(splits >= 1, TG_ERR_ARG, "%s: splits (%d) must be >= 1 (ask tg_attention_wide_splits for the planner's choice)", who, splits);
+  const long nt = wide_tiles(d), S = splits < nt ? splits : nt;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (S == 1) return dispatch_wide<false>(d, st, 1, nullptr, who, key_mask, key_mask_bs);
+  TG_CHECK(workspace != nullptr && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, TG_ERR_ARG, "%s: workspace must be non-null and 16-byte aligned", who);
+  const long need = wide_ws_bytes(d, S);
+  TG_CHECK(workspace_bytes >= need, TG_ERR_ARG, "%s: workspace of %lld bytes, %d splits need %ld", who, (long long)workspace_bytes, (int)S, need);
+  return dispatch_wide<true>(d, st, (int)S, static_cast<float*>(workspace), who, key_mask, key_mask_bs);
 }

@@ -622,6 +622,57 @@ def attention_swin(q, q_ld, q_bs, k, k_ld, k_bs, v, v_ld, v_bs, pad_q, pad_k, pa
     return out
 
 
+def _held(t):
+    """elements of ``t``'s storage from its first element on"""
+    return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+
+
+def msdeform_attn(value, v_ld, v_bs, shapes, offsets, off_ld, logits, log_ld, ref, batch, heads, n_q, out, out_ld, out_bs, value_mask=None,
+                  head_dim=32, n_points=4):
+    """``tg_msdeform_attn``: multi-scale deformable attention from the projected operands on (transformers' GroundingDinoMultiscaleDeformableAttention
+    between its projections).  ``value`` [batch, Nv, heads * 32] (row pitch ``v_ld``, batch pitch ``v_bs``, elements), Nv = the tokens of the levels
+    ``shapes`` = [(H_l, W_l), ...] concatenated; ``offsets`` rows [batch * n_q] of heads * L * 4 * 2 values (x, y in pixels of the level) and ``logits``
+    rows of heads * L * 4, each with its row pitch (two column slices of one GEMM output); ``ref`` fp32 [batch, n_q, L, R], R = 2 (centres) or 4
+    (boxes); ``value_mask`` uint8 [batch, Nv], 1 = padding token (samples as zeros).  Writes ``out`` [batch, n_q, heads * 32]."""
+    _need_cuda(value)
+    batch, heads, n_q = int(batch), int(heads), int(n_q)
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    L = len(shapes)
+    nv = sum(h * w for h, w in shapes)
+    hd = heads * int(head_dim)
+    if batch < 1 or heads < 1 or n_q < 1 or nv < 1 or any(h < 1 or w < 1 for h, w in shapes):
+        raise RuntimeError(f"msdeform_attn: empty problem (batch {batch}, heads {heads}, n_q {n_q}, levels {shapes})")
+    _f32_dev(ref, "msdeform_attn: ref")
+    if ref.ndim != 4 or tuple(ref.shape[:3]) != (batch, n_q, L):
+        raise RuntimeError(f"msdeform_attn: ref must be [{batch}, {n_q}, {L}, 2 or 4], got {tuple(ref.shape)}")
+    R = int(ref.shape[3])
+    for name, t, rows, ld, bs, cols in (("value", value, nv, v_ld, v_bs, hd), ("out", out, n_q, out_ld, out_bs, hd),
+                                        ("offsets", offsets, batch * n_q, off_ld, None, heads * L * int(n_points) * 2),
+                                        ("logits", logits, batch * n_q, log_ld, None, heads * L * int(n_points))):
+        _need_cuda(t)
+        if t.dtype != value.dtype or t.device != value.device:
+            raise RuntimeError(f"msdeform_attn: {name} must be a {value.dtype} tensor on {value.device}, got {t.dtype} on {t.device}")
+        if t.stride(-1) != 1:
+            raise RuntimeError(f"msdeform_attn: {name} must have unit stride along the channels")
+        if int(ld) < cols or (bs is not None and (int(bs) < 0 or (name == "out" and batch > 1 and int(bs) < (rows - 1) * int(ld) + cols))):
+            raise RuntimeError(f"msdeform_attn: {name} pitches (row {ld}, batch {bs}) do not hold {rows} rows of {cols} channels without overlap")
+        # the last element the kernel touches must lie inside the tensor's storage (the C entry point cannot know buffer sizes)
+        need = ((batch - 1) * int(bs) if bs is not None else 0) + (rows - 1) * int(ld) + cols
+        if _held(t) < need:
+            raise RuntimeError(f"msdeform_attn: {name} holds {_held(t)} elements from its first, {need} are addressed ({rows} rows, row pitch {ld}, "
+                               f"batch {batch}, batch pitch {bs})")
+    if value_mask is not None:
+        _need_cuda(value_mask)
+        if value_mask.dtype != torch.uint8 or not value_mask.is_contiguous() or value_mask.numel() != batch * nv or value_mask.device != value.device:
+            raise RuntimeError(f"msdeform_attn: value_mask must be a contiguous uint8 tensor [{batch}, {nv}] on {value.device}, "
+                               f"got {tuple(value_mask.shape)} {value_mask.dtype}")
+    sh = (C.c_int32 * (2 * L))(*[v for hw in shapes for v in hw])
+    _lib.check(_lib.lib().tg_msdeform_attn(_dt(value), batch, heads, int(head_dim), L, int(n_points), n_q, R, sh, _ptr(value), int(v_ld), int(v_bs),
+                                           _ptr(offsets), int(off_ld), _ptr(logits), int(log_ld), _ptr(ref), _ptr(value_mask), _ptr(out),
+                                           int(out_ld), int(out_bs), _stream()))
+    return out
+
+
 def _f32_dev(t, what, numel=None):
     _need_cuda(t)
     if t.dtype != torch.float32 or not t.is_contiguous() or (numel is not None and t.numel() != numel):
@@ -706,14 +757,26 @@ def sam_mask_post(logits, padded_size, reshaped_size, original_size, target_size
     return mask, areas
 
 
-def attention_wide(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale, out, out_ld, out_bs, key_splits=None):
+def attention_wide(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale, out, out_ld, out_bs, key_splits=None,
+                   key_mask=None):
     """``tg_attention_wide``: one-segment flash attention for head dims 256 / 512 (the VAE mid block), the argument list of ``attention`` without
     the second segment, mask, causal flag and device scalar.  Another head dim is an error (``attention`` takes multiples of 8 up to 160).
     ``key_splits``: None / 1 = the unsplit launch; 0 = the planner's choice (``tg_attention_wide_splits``), n >= 2 = n splits (clamped to the number of
     32-key tiles).  More than one effective split runs ``tg_attention_wide_split``: a partial launch and a combine launch, fp32 partials in the
-    persistent ``workspace`` of the current slot (``tg_attention_wide_workspace_bytes``)."""
+    persistent ``workspace`` of the current slot (``tg_attention_wide_workspace_bytes``).
+    ``key_mask``: uint8 [batch, len0], 1 = the key is masked for every query of its batch item (``tg_attention_wide_kmask``; a key-padding mask).  It
+    also serves a key count that is no multiple of 8: pad ``len0`` (and the V^T pitch) to one and mask the tail.  A row whose keys are ALL masked
+    is outside the contract and comes out as zeros."""
     _need_cuda(q)
     d = _attn_desc(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, batch, heads, head_dim, n_q, scale, out, out_ld, out_bs)
+    if key_mask is not None:
+        if (not isinstance(key_mask, torch.Tensor) or key_mask.dtype != torch.uint8 or key_mask.ndim != 2
+                or tuple(key_mask.shape) != (int(batch), int(len0)) or not key_mask.is_contiguous()):
+            raise RuntimeError(f"attention_wide: key_mask must be a contiguous uint8 tensor [{int(batch)}, {int(len0)}] (1 = masked), got "
+                               f"{tuple(key_mask.shape) if isinstance(key_mask, torch.Tensor) else type(key_mask)} "
+                               f"{getattr(key_mask, 'dtype', '')}")
+        if not key_mask.is_cuda or key_mask.device != q.device:
+            raise RuntimeError(f"attention_wide: key_mask must live on {q.device}")
     L = _lib.lib()
     S = 1
     if key_splits is not None and int(key_splits) != 1:
@@ -722,7 +785,11 @@ def attention_wide(q, q_ld, q_bs, k0, k0_ld, k0_bs, vt0, vt0_ld, vt0_bs, len0, b
         S = L.tg_attention_wide_splits(C.byref(d), int(key_splits))
         if S < 0:
             _lib.check(S)                                                    # a refused descriptor: the code and message of the library
-    if S > 1:
+    if key_mask is not None:
+        ws = workspace(int(L.tg_attention_wide_workspace_bytes(C.byref(d), S)), q.device) if S > 1 else None
+        launch = lambda: _lib.check(L.tg_attention_wide_kmask(C.byref(d), key_mask.data_ptr(), int(len0), max(S, 1), _ptr(ws),   # noqa: E731
+                                                              ws.numel() * 4 if ws is not None else 0, _stream()))
+    elif S > 1:
         nbytes = int(L.tg_attention_wide_workspace_bytes(C.byref(d), S))
         ws = workspace(nbytes, q.device)
         launch = lambda: _lib.check(L.tg_attention_wide_split(C.byref(d), S, ws.data_ptr(), ws.numel() * 4, _stream()))   # noqa: E731
@@ -865,6 +932,28 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
         out = torch.empty((rows, Cc), dtype=x.dtype, device=x.device)
     _lib.check(_lib.lib().tg_layernorm(_dt(x), _ptr(x), rows, Cc, x.stride(0), float(eps), _ptr(gamma), _ptr(beta), _ptr(out),
                                        out.stride(0), _stream()))
+    return out
+
+
+def layernorm_add(x, res, gamma, beta, eps=1e-5, out=None):
+    """``tg_layernorm_add``: LN(x + res) with the sum taken in fp32 from the two stored operands (a post-norm residual block without the rounding of
+    the sum that a residual GEMM epilogue + ``layernorm`` has).  x, res [rows, C] (any row pitch, unit channel stride); gamma, beta [C]."""
+    _need_cuda(x)
+    rows, Cc = x.shape
+    for name, t in (("res", res), ("gamma", gamma), ("beta", beta)):
+        _need_cuda(t)
+        if t.dtype != x.dtype or t.device != x.device:
+            raise RuntimeError(f"layernorm_add: {name} must be a {x.dtype} tensor on {x.device}, got {t.dtype} on {t.device}")
+    if tuple(res.shape) != (rows, Cc) or x.stride(1) != 1 or res.stride(1) != 1 or gamma.numel() != Cc or beta.numel() != Cc \
+            or not gamma.is_contiguous() or not beta.is_contiguous():
+        raise RuntimeError(f"layernorm_add: x and res must be [rows, C] with unit channel stride and gamma, beta contiguous [C]; got {tuple(x.shape)}, "
+                           f"{tuple(res.shape)}, {tuple(gamma.shape)}, {tuple(beta.shape)}")
+    if out is None:
+        out = torch.empty((rows, Cc), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or out.device != x.device or tuple(out.shape) != (rows, Cc) or out.stride(1) != 1:
+        raise RuntimeError(f"layernorm_add: out must be a {x.dtype} tensor [{rows}, {Cc}] on {x.device} with unit channel stride")
+    _lib.check(_lib.lib().tg_layernorm_add(_dt(x), _ptr(x), x.stride(0), _ptr(res), res.stride(0), rows, Cc, float(eps), _ptr(gamma), _ptr(beta),
+                                           _ptr(out), out.stride(0), _stream()))
     return out
 
 

@@ -772,7 +772,9 @@ int tg_guidance_plan_run(const tg_guidance_pitem* items_device, int32_t n_items,
  * (ip_adapter/attention_processor.py:113-128) and `Transformer2DModel.proj_in / proj_out` (models/transformer_2d.py:150-163) at the
  * first UNet level.  `wpk`: N / 64 chunks of (128 K + 1024) bytes: the chunk's weight fragments, then one vector page (fp32 v[64]:
  * bias, or W beta + bias with the fold; fp32 u[64]: row sums of the rounded W gamma, fold only).  `ln` != 0: x is the UN-normalised
- * stream, statistics per row in fp32 (two-pass, as tg_layernorm).  `variant`: reserved, must be 0. */
+ * stream, statistics per row in fp32 (two-pass, as tg_layernorm).  `variant`: reserved, must be 0.
+ * Alignment (all row-chain entries): every row and weight-stream operand is moved in 16-byte pieces, so x / h, res, out, y, qk, coef, the packed streams, kv and
+ * tg_rc_kv_pack's k / kip / out must be 16-byte aligned (TG_ERR_ARG before any launch otherwise); V^T tensors are accessed element-wise and need no alignment. */
 typedef struct {
   int32_t dtype;
   const void* x; int64_t ldx;
@@ -799,7 +801,8 @@ int tg_rc_linear_dup(const tg_rc_linear_desc* d, int64_t c_dup_offset, void* str
  * permuted weights (theatergen_amd/rowchain.py: LayerNorm and softmax scale * log2(e) folded into wq); `kv`: tg_rc_kv_pack output
  * [batch][8][24 KiB]; `ip_scale`: DEVICE fp32 scalar (IPAttnProcessor.scale, graph-replayable) or NULL (= 1).
  * tg_rc_kv_pack: text K [batch * text_len, 320] / V^T [batch, 320, ldt] and image K [batch * ip_tokens, 320] / V^T [batch, 320, ldi]
- * (the layouts IPAttnProcessor's projection GEMMs write) -> `out` fragments, batch * 8 * 24 KiB. */
+ * (the layouts IPAttnProcessor's projection GEMMs write) -> `out` fragments, batch * 8 * 24 KiB.  ldt >= text_len and (ip_tokens > 0) ldi >= ip_tokens, or
+ * TG_ERR_ARG: a V^T row shorter than its key count would be read into the next channel's row. */
 typedef struct {
   int32_t dtype;
   const void* h; int64_t ldh;

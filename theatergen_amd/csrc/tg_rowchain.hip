@@ -1752,6 +1752,9 @@ int launch_rc_linear(const tg_rc_linear_desc* d, const RcLinearParams& p, hipStr
   return TG_OK;
 }
 
+// every row / weight-stream operand is moved in 16-byte pieces (global loads and stores, LDS-DMA, f32x4 coefficient reads)
+inline bool rc_al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
 }  // namespace
 
 extern "C" int tg_rc_linear(const tg_rc_linear_desc* d, void* stream) { return tg_rc_linear_dup(d, 0, stream); }
@@ -1765,6 +1768,7 @@ extern "C" int tg_rc_linear_dup(const tg_rc_linear_desc* d, int64_t c_dup_offset
   TG_CHECK(d->M > 0 && d->x && d->wpk && d->out, TG_ERR_ARG, "tg_rc_linear: null operand or M <= 0");
   TG_CHECK(d->ldx >= d->K && d->ldx % 8 == 0 && d->ldc >= d->N && d->ldc % 8 == 0, TG_ERR_ARG, "tg_rc_linear: row pitches must be multiples of 8 elements");
   TG_CHECK(!d->res || (d->ldres >= d->N && d->ldres % 8 == 0), TG_ERR_ARG, "tg_rc_linear: residual pitch");
+  TG_CHECK(rc_al16(d->x) && rc_al16(d->wpk) && rc_al16(d->res) && rc_al16(d->out), TG_ERR_ARG, "tg_rc_linear: x, wpk, res and out must be 16-byte aligned");
   TG_CHECK(c_dup_offset == 0 || (c_dup_offset % 8 == 0 && c_dup_offset >= (d->M - 1) * d->ldc + d->N), TG_ERR_ARG,
            "tg_rc_linear_dup: c_dup_offset = %lld must be a multiple of 8 elements past the first destination", (long long)c_dup_offset);
   RcLinearParams p;
@@ -1785,6 +1789,8 @@ extern "C" int tg_rc_xattn_ps(const tg_rc_xattn_desc* d, int32_t ip_scale_count,
   TG_CHECK(d->rows_per_batch > 0 && d->rows_per_batch % 128 == 0 && d->M % d->rows_per_batch == 0, TG_ERR_ARG,
            "tg_rc_xattn: rows_per_batch = %d must be a multiple of 128 that divides M (a workgroup's 128 tokens share one key set)", d->rows_per_batch);
   TG_CHECK(d->ldh >= 320 && d->ldh % 8 == 0 && d->ldc >= 320 && d->ldc % 8 == 0, TG_ERR_ARG, "tg_rc_xattn: row pitches");
+  TG_CHECK(rc_al16(d->h) && rc_al16(d->wq) && rc_al16(d->kv) && rc_al16(d->wo) && rc_al16(d->out), TG_ERR_ARG,
+           "tg_rc_xattn: h, wq, kv, wo and out must be 16-byte aligned");
   TG_CHECK(ip_scale_count == 0 || ip_scale_count == 1 || ip_scale_count == d->M / d->rows_per_batch, TG_ERR_ARG,
            "tg_rc_xattn_ps: ip_scale_count = %d (0 or 1: ip_scale is one float; M / rows_per_batch = %lld: one per batch item)", ip_scale_count,
            (long long)(d->M / d->rows_per_batch));
@@ -1806,6 +1812,9 @@ extern "C" int tg_rc_kv_pack(int32_t dtype, int32_t batch, const void* k, const 
   TG_CHECK(batch > 0 && k && vt && out, TG_ERR_ARG, "tg_rc_kv_pack: null operand");
   TG_CHECK(text_len > 0 && text_len <= 80 && ip_tokens >= 0 && ip_tokens <= 16 && (ip_tokens == 0 || (kip && vtip)), TG_ERR_ARG,
            "tg_rc_kv_pack: %d text keys (<= 80), %d image keys (<= 16)", text_len, ip_tokens);
+  TG_CHECK(ldt >= text_len && (ip_tokens == 0 || ldi >= ip_tokens), TG_ERR_ARG,
+           "tg_rc_kv_pack: V^T row pitches %lld / %lld below the key counts %d / %d", (long long)ldt, (long long)ldi, text_len, ip_tokens);
+  TG_CHECK(rc_al16(k) && rc_al16(out) && (ip_tokens == 0 || rc_al16(kip)), TG_ERR_ARG, "tg_rc_kv_pack: k, kip and out must be 16-byte aligned");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = (unsigned)batch * 8 * 24;
   if (dtype == TG_BF16)
@@ -1843,6 +1852,8 @@ extern "C" int tg_rc_front(const tg_rc_front_desc* d, void* stream) {
   TG_CHECK(d->ldx >= 320 && d->ldx % 8 == 0 && d->ldy >= 320 && d->ldy % 8 == 0 && d->ldqk >= 640 && d->ldqk % 8 == 0 && d->ldt >= d->rows_per_batch,
            TG_ERR_ARG, "tg_rc_front: row pitches");
   TG_CHECK(d->dbg == 0, TG_ERR_ARG, "tg_rc_front: dbg = %d (reserved, must be 0)", d->dbg);
+  TG_CHECK(rc_al16(d->x) && rc_al16(d->coef) && rc_al16(d->win) && rc_al16(d->wqkv) && rc_al16(d->y) && rc_al16(d->qk), TG_ERR_ARG,
+           "tg_rc_front: x, coef, win, wqkv, y and qk must be 16-byte aligned");
   RcFrontParams p;
   p.x = d->x; p.ldx = d->ldx; p.coef = d->coef; p.win = d->win; p.wqkv = d->wqkv; p.y = d->y; p.ldy = d->ldy; p.qk = d->qk; p.ldqk = d->ldqk;
   p.vt = d->vt; p.ldt = d->ldt; p.M = d->M; p.rows_per_batch = d->rows_per_batch; p.ln_eps = d->ln_eps;

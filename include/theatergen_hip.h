@@ -466,6 +466,45 @@ int tg_attn_probs(int32_t dtype, int32_t batch, int32_t b0, int32_t heads, int32
  *   (models/unet_2d_condition.py:1015-1017).
  * tg_layernorm: LayerNorm(C, eps) per row: BasicTransformerBlock.norm1/2/3 (models/attention.py:186, 206, 226),
  *   Resampler norms (ip_adapter/resampler.py:43-44, 66-67, 100).  gamma/beta may be NULL.
+ *
+ * The forward contracts (restated in fp64 in tests/norm_contract.py; every launch state below is entered by tests/test_norm_edges_gpu.py;
+ * the figures are those of the fp32 CPU model of the kernels against the fp64 restatement: profiles/norm_contract_findings.md).
+ *
+ * GroupNorm.  x[b, p, :] = [x0[b, p, 0..c0) | x1[b, p, 0..c1)] (both dense, pixel pitch c0 / c1; x1 NULL: c1 is taken as 0), C = c0 + c1,
+ * group g = channels [g C / groups, (g + 1) C / groups).  Per (b, g) over the hw pixels and C / groups channels:
+ *     mean = E[x],  var = E[(x - mean)^2] (biased),  rstd = (var + eps)^-1/2
+ *     a[b, c] = rstd gamma[c] (gamma NULL: rstd),  d[b, c] = beta[c] - mean a[b, c] (beta NULL: - mean a[b, c])
+ *     tg_groupnorm:      out[b, p, c] = act(x[b, p, c] a[b, c] + d[b, c]) rounded once to the storage dtype; act = SiLU (silu != 0) or identity
+ *     tg_groupnorm_coef: coef[b][0][c] = a[b, c], coef[b][1][c] = d[b, c] in fp32
+ *   Which kernel runs:
+ *     one launch, two passes (mean, then the centred sum of squares, the item's slab held in registers) when hw <= 256, C / groups is a
+ *       multiple of 8, gamma and beta are 16-byte aligned (or NULL), and the block shape fits: gpb = the smallest divisor of `groups` with
+ *       gpb C / groups >= 64 (or `groups` itself) is <= 16, gpb C / groups / 8 <= 256 chunk columns, <= 24 pixels per pixel lane.  The
+ *       scratch is not touched.
+ *     two launches otherwise: fp32 sums of x and x^2 per (item, pixel slab, group) into `partials` ([batch][nblk][groups][2], nblk =
+ *       min(max(hw / 8, 1), max(512 / batch, 1)); the 2 * batch * groups floats behind them are reserved and not written), folded IN FP64 in a
+ *       fixed order by every block of the apply pass: mean = S / n, var = max(Q / n - mean^2, 0).  The variance is therefore taken in ONE
+ *       pass from fp32 slab sums.  With R = |mean| / std of a group: up to R = 64 the output stays on the floor of one rounding to the
+ *       storage dtype (fp16, 1 x 1024 x 320 / 32 groups: rel-L2 1.00 x the floor up to R = 16, 1.05 x at R = 64, relative rstd error
+ *       9e-5; 1 x 288 x 2560: 1.07 x, rstd error 1.2e-4; bf16 <= 1.01 x, rstd error <= 4.3e-4), which is the bound the tests hold it to
+ *       without allowance.  R = 256 is OUTSIDE the contract: fp16 4.8 x and 5.3 x the floor on these two shapes (rel-L2 1.0e-3 and 1.1e-3,
+ *       rstd error 1.3e-3 and 2.7e-3), bf16 on the 80-channel groups 2.4 x (on 10-channel groups every bf16 sum is exact).  The one-launch
+ *       path and both LayerNorm kernels centre before squaring and stay on the floor at any R the storage dtype can hold.
+ *   Both paths are deterministic (no atomics, fixed-order folds).  A batch item launched alone gives the bits of the batched launch on the
+ *   one-launch path, and on the two-launch path when nblk is the same for both batch sizes.  tg_groupnorm_coef followed by the expression
+ *   above gives tg_groupnorm's bits (the conv kernels that take `a_coef` rely on it).  out must not overlap x0, x1, gamma or beta.
+ *   TG_ERR_ARG, before any launch: bad dtype; NULL x0, out (coef), partials; batch, hw or groups < 1; batch > 65535; c0 or c1 not a multiple
+ *   of 8; C not a multiple of groups; C > 8192; x0, x1 or out not 16-byte aligned; tg_groupnorm_coef: groups > 256.  gamma and beta need
+ *   2-byte alignment only (without 16 the two-launch path runs).
+ *
+ * LayerNorm.  Per row r of x [rows][C] (row pitch ldx elements): mean = E[x[r, :]], var = E[(x[r, :] - mean)^2] (biased, two passes in fp32
+ * registers), rstd = (var + eps)^-1/2.
+ *     tg_layernorm:       out[r, c] = (x[r, c] - mean) rstd (* gamma[c]) (+ beta[c]) rounded once, row pitch ldo; gamma / beta NULL: left out
+ *     tg_layernorm_stats: stats[r] = (rstd, -rstd mean) in fp32, so that x stats[r][0] + stats[r][1] is the normalised row
+ *   out may be x itself (same pointer and pitch: a row is read completely before it is written, by the lanes that write it); any other
+ *   overlap of out with x, gamma or beta is not allowed.  Deterministic; a row's result does not depend on `rows`.
+ *   TG_ERR_ARG, before any launch: bad dtype; NULL x, out (stats); rows < 1; C < 8, not a multiple of 8 or > 4096; ldx or ldo not a
+ *   multiple of 8 or below C; x, out, a non-NULL gamma or beta not 16-byte aligned; stats not 8-byte aligned.
  */
 int64_t tg_groupnorm_scratch_bytes(int32_t batch, int64_t hw, int32_t groups);
 int tg_groupnorm(int32_t dtype, const void* x0, const void* x1, int32_t c0, int32_t c1, int32_t batch, int64_t hw,
@@ -498,7 +537,12 @@ int tg_groupnorm_coef(int32_t dtype, const void* x0, const void* x1, int32_t c0,
 /* tg_groupnorm / tg_groupnorm_coef from partial sums a producer already wrote (tg_gemm_desc.out_gn_partials: fp32 [batch][nblk][groups][2], one entry per
  * 64-pixel block): the statistics launch is skipped.  `coef` != NULL: the coefficients (x is not read); else `out` = the normalised (+ SiLU) tensor of the
  * single-source x [batch, hw, C].  The fold of the partials (fp64, fixed order) and the apply expressions are tg_groupnorm's; the sums were accumulated in a
- * different order than gn_partial_kernel's, so results agree with tg_groupnorm to rounding of the statistics, not bit for bit. */
+ * different order than gn_partial_kernel's, so results agree with tg_groupnorm to rounding of the statistics, not bit for bit.
+ *   Contract: S = sum_k partials[b][k][g][0], Q = sum_k partials[b][k][g][1] over k < nblk (the PRODUCER's block count, whatever slab count the apply pass
+ *   uses), n = hw C / groups, mean = S / n, var = max(Q / n - mean^2, 0), then a, d, out and coef as for tg_groupnorm.  No path choice: coef mode is one
+ *   block per item, apply mode the second launch of the two-launch path; no scratch.  out must not overlap x, gamma, beta or partials.
+ *   TG_ERR_ARG, before any launch: bad dtype; NULL partials; nblk < 1; coef NULL and (x or out NULL, or not 16-byte aligned); batch, hw or groups < 1;
+ *   batch > 65535; groups > 256; C not a multiple of 8 or of groups; C > 8192. */
 int tg_groupnorm_from_partials(int32_t dtype, const void* x, int32_t C, int32_t batch, int64_t hw, int32_t groups, float eps, const void* gamma,
                                const void* beta, int32_t silu, void* out, float* coef, const float* partials, int32_t nblk, void* stream);
 

@@ -112,6 +112,8 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(GnParams p) {
 // through LDS -> deterministic.  Runs as the prologue of the apply kernel (each block re-derives the 32 group
 // statistics of its batch item from <= 16 KB of L2-resident partials) instead of as a launch of its own: one launch
 // and ~5 us less per GroupNorm, 61 GroupNorms per UNet call.
+// ONE-PASS variance (E[x^2] - mean^2) from fp32 slab sums: on the floor of the storage rounding up to |mean| / std = 64, outside the
+// contract at 256 (include/theatergen_hip.h "GroupNorm"; gn_small_kernel and the LayerNorm kernels centre before squaring).
 __device__ __forceinline__ void gn_block_stats(const GnParams& p, int b, float* s_stats /* [groups][2] in LDS */) {
   __shared__ double sh[8][32][2];
   const int C = p.c0 + p.c1;
@@ -502,6 +504,9 @@ int groupnorm_impl(int32_t dtype, const void* x0, const void* x1, int32_t c0, in
   TG_CHECK(batch > 0 && hw > 0 && groups > 0 && C % groups == 0 && c0 % 8 == 0 && c1 % 8 == 0, TG_ERR_ARG,
            "tg_groupnorm: bad shape batch=%d hw=%lld C=%d+%d groups=%d", batch, (long long)hw, c0, c1, groups);
   TG_CHECK(C <= 8 * 256 * GN_MAX_CHUNKS, TG_ERR_ARG, "tg_groupnorm: C too large");
+  TG_CHECK(batch <= 65535, TG_ERR_ARG, "tg_groupnorm: batch %d above the grid's y limit (65535)", batch);
+  TG_CHECK((reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(x1) | reinterpret_cast<uintptr_t>(out)) % 16 == 0, TG_ERR_ARG,
+           "tg_groupnorm: x0, x1 and out must be 16-byte aligned");
   GnParams p{};
   p.x0 = x0; p.x1 = x1; p.c0 = c0; p.c1 = c1; p.batch = batch; p.hw = hw; p.groups = groups; p.eps = eps;
   p.gamma = gamma; p.beta = beta; p.silu = silu; p.out = out; p.coef = coef;
@@ -571,6 +576,9 @@ extern "C" int tg_layernorm(int32_t dtype, const void* x, int64_t rows, int32_t 
   TG_CHECK(dtype == TG_BF16 || dtype == TG_F16, TG_ERR_ARG, "tg_layernorm: bad dtype");
   TG_CHECK(x && out && rows > 0 && C > 0 && C % 8 == 0 && C <= 8 * 64 * 8 && ldx % 8 == 0 && ldo % 8 == 0, TG_ERR_ARG,
            "tg_layernorm: bad args rows=%lld C=%d", (long long)rows, C);
+  TG_CHECK(ldx >= C && ldo >= C, TG_ERR_ARG, "tg_layernorm: row pitches ldx=%lld ldo=%lld must cover C=%d", (long long)ldx, (long long)ldo, C);
+  TG_CHECK((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta)) % 16 == 0,
+           TG_ERR_ARG, "tg_layernorm: x, out, gamma and beta must be 16-byte aligned");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (dtype == TG_BF16) return launch_ln<bf16_t>(x, rows, C, ldx, eps, gamma, beta, out, ldo, st);
   return launch_ln<f16_t>(x, rows, C, ldx, eps, gamma, beta, out, ldo, st);
@@ -582,6 +590,9 @@ extern "C" int tg_groupnorm_from_partials(int32_t dtype, const void* x, int32_t 
   TG_CHECK(partials != nullptr && nblk > 0 && (coef != nullptr || (x != nullptr && out != nullptr)), TG_ERR_ARG, "tg_groupnorm_from_partials: null pointer");
   TG_CHECK(batch > 0 && hw > 0 && groups > 0 && groups <= 256 && C % groups == 0 && C % 8 == 0 && C <= 8 * 256 * GN_MAX_CHUNKS, TG_ERR_ARG,
            "tg_groupnorm_from_partials: bad shape batch=%d hw=%lld C=%d groups=%d", batch, (long long)hw, C, groups);
+  TG_CHECK(batch <= 65535, TG_ERR_ARG, "tg_groupnorm_from_partials: batch %d above the grid's y limit (65535)", batch);
+  TG_CHECK(coef != nullptr || (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) % 16 == 0, TG_ERR_ARG,
+           "tg_groupnorm_from_partials: x and out must be 16-byte aligned");
   GnParams p{};
   p.x0 = x; p.x1 = nullptr; p.c0 = C; p.c1 = 0; p.batch = batch; p.hw = hw; p.groups = groups; p.eps = eps;
   p.gamma = gamma; p.beta = beta; p.silu = silu; p.out = out; p.coef = coef;
@@ -609,6 +620,8 @@ extern "C" int tg_layernorm_stats(int32_t dtype, const void* x, int64_t rows, in
   TG_CHECK(dtype == TG_BF16 || dtype == TG_F16, TG_ERR_ARG, "tg_layernorm_stats: bad dtype");
   TG_CHECK(x && stats && rows > 0 && C > 0 && C % 8 == 0 && C <= 8 * 64 * 8 && ldx % 8 == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0, TG_ERR_ARG,
            "tg_layernorm_stats: bad args rows=%lld C=%d", (long long)rows, C);
+  TG_CHECK(ldx >= C && reinterpret_cast<uintptr_t>(x) % 16 == 0, TG_ERR_ARG, "tg_layernorm_stats: ldx=%lld must cover C=%d and x must be 16-byte aligned",
+           (long long)ldx, C);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (dtype == TG_BF16) return launch_ln<bf16_t>(x, rows, C, ldx, eps, nullptr, nullptr, nullptr, 0, st, stats);
   return launch_ln<f16_t>(x, rows, C, ldx, eps, nullptr, nullptr, nullptr, 0, st, stats);

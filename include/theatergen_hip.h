@@ -202,6 +202,29 @@ int tg_conv_up2(const tg_gemm_desc* d, void* stream);
  * k{0,1}[b, j, h*d + c] likewise; vt{0,1} is V TRANSPOSED per batch: vt[b, h*d + c, j], row pitch vt_ld
  * (multiple of 8), batch pitch vt_bs.  out[b, i, h*d + c].  head_dim in {40, 64, 80, 160} (or any
  * multiple of 8 <= 160).  len1 == 0 disables segment 1.
+ * Arithmetic: scores are accumulated in fp32 from the stored q / k, the softmax is online over 64-key tiles with a reference that moves lazily (by
+ * more than 8 exp2 units at a time, decided per 32 query rows), P is rounded to the storage dtype where it enters the PV product, O is accumulated in fp32
+ * and rounded once.  ONE instance differs: head_dim 40 WITHOUT a mask (the SD-1.5 level-0 layers) multiplies the query by scale * log2(e) and ROUNDS
+ * IT BACK TO THE STORAGE DTYPE, and keeps the softmax reference as a storage-dtype value, so that the QK^T product delivers exp2's argument.  Measured
+ * against fp64 on N(0, 1) operands (whole-tensor rel-L2, bf16 / fp16; the same operands through the head-dim-40 instance that does not round, in
+ * brackets): 2.8e-3 / 3.5e-4 (2.2e-3 / 2.7e-4); with the query x 2, x 4, x 8 — scores of standard deviation 2, 4, 8 — 3.2e-3, 3.7e-3, 4.7e-3 / 4.0e-4,
+ * 4.6e-4, 5.8e-4 (1.9e-3, 1.8e-3, 1.6e-3 / 2.4e-4, 2.2e-4, 2.1e-4).  The suite's per-launch figure for attention, 4.5e-3 / 6e-4, therefore holds
+ * up to a score deviation of 4 in bf16 (worst 128-query block 3.8e-3) and is missed at 8 (4.9e-3 in the worst block); fp16 stays inside at 8.  Whether
+ * the scores of the production head-dim-40 layers reach that spread has not been measured.  The storage-dtype reference also bounds the scores this
+ * instance takes at all: it sits up to 2^-9 (bf16) / 2^-12 (fp16) of the row maximum away from it, so |scale * log2(e) * q.k| must stay below
+ * about 2^15 / 2^18; every other instance keeps the reference in fp32.
+ * Mask values (the instances with a mask; profiles/attn_fwd_contract_findings.md): any finite value and -inf.  A masked key contributes exactly 0
+ * wherever its row has a visible key, in whatever order they come: while a row has seen no visible key (its tiles so far hold -inf only, or values
+ * whose mask / scale overflows to -inf, such as finfo(float32).min) probabilities are formed against the reference 0, as tg_attention_wide_kmask
+ * does.  A row whose keys ALL carry -inf is outside the contract and gives NaN (as torch.softmax does).  A row whose keys all carry the same huge
+ * finite value (-1e30) is uniform: from a reference of 2^24 exp2 units on, the reference is subtracted from the score before the multiply by
+ * scale * log2(e).  Rows below that keep the bits they had before these two rules existed.
+ * Validation is on the host, before any launch; a refused descriptor writes nothing.  TG_ERR_ARG: null descriptor / q / k0 / vt0 / out, bad dtype,
+ * batch / heads / n_q / len0 <= 0, head_dim no multiple of 8 in 8..160, q_ld / k0_ld / vt0_ld no multiple of 8 or out_ld none of 4 (the 16-byte
+ * loads and LDS-DMA requests and the 8-byte stores), len1 outside 0..64, with len1 > 0 a null k1 / vt1 or k1_ld / vt1_ld no multiple of 8,
+ * !(scale > 0) (the lazy reference and the mask's 1 / scale assume it; with or without a mask), q / k0 / vt0 (k1 / vt1 when len1 > 0) not 16-byte
+ * aligned, out not 8-byte aligned, mask not 4-byte aligned, vt0_ld < len0 or vt1_ld < len1, and with batch > 1 a batch stride that breaks the
+ * same alignment (q_bs, k0_bs, vt0_bs, and k1_bs, vt1_bs when len1 > 0, multiples of 8; out_bs of 4).
  */
 typedef struct {
   int32_t dtype;

@@ -292,10 +292,29 @@ def attention_read_extents(a):
         regs.append(Region("k" + s, a["k" + s], 0, (B, L, HD), (int(a[f"k{s}_bs"]), int(a[f"k{s}_ld"]), 1)))
         regs.append(Region("vt" + s, a["vt" + s], 0, (B, HD, L), (int(a[f"vt{s}_bs"]), int(a[f"vt{s}_ld"]), 1)))
     if a.get("mask") is not None:
-        regs.append(Region("mask", a["mask"], 0, (a["mask"].numel(),), (1,)))
-    if a.get("w1_dev") is not None:
-        regs.append(Region("w1_dev", a["w1_dev"], 0, (1,), (1,)))
+        bs, hs, qs = attention_mask_strides(a)
+        # exactly the elements read: a zero stride reads one item / head / row for all
+        regs.append(Region("mask", a["mask"], 0, (B if bs else 1, int(a["heads"]) if hs else 1, nq if qs else 1, int(a["len0"])), (bs, hs, qs, 1)))
+    if a.get("w1_dev") is not None and int(a["len1"]) > 0:
+        regs.append(Region("w1_dev", a["w1_dev"], 0, (attention_w1_count(a),), (1,)))
     return regs
+
+
+def attention_mask_strides(a):
+    """(mask_bs, mask_hs, mask_qs) in elements: the descriptor's own fields where the dict has them (the mask is then a pointer), else what
+    ``ops.attention`` derives from a contiguous [Bm, Hm, Qm, len0] tensor"""
+    if "mask_bs" in a:
+        return int(a["mask_bs"]), int(a["mask_hs"]), int(a["mask_qs"])
+    bm, hm, qm, L = a["mask"].shape
+    return (hm * qm * L if bm > 1 else 0), (qm * L if hm > 1 else 0), (L if qm > 1 else 0)
+
+
+def attention_w1_count(a):
+    """floats behind ``w1_dev``: ``ip_scale_count`` of tg_attention_ps where the dict has it (0 and 1 both mean one), else ``ops.attention``'s
+    rule (a tensor of ``batch`` elements is per item)"""
+    if a.get("ip_scale_count") is not None:
+        return max(1, int(a["ip_scale_count"]))
+    return int(a["batch"]) if a["w1_dev"].numel() == int(a["batch"]) else 1
 
 
 # ---- attention ---------------------------------------------------------------------------------------------------------------------
@@ -312,14 +331,22 @@ def _segment(q, k, vt, scale, bias=None, causal=False, q0=0):
 
 
 def attention_reference(q_chunk=2048, **a):
-    """fp64 [batch, n_q, heads * head_dim]: O = softmax(s Q K0^T + mask) V0 + w1 softmax(s Q K1^T) V1, per (batch item, head) and
-    query chunk so that self-attention at n = 9216 fits"""
+    """fp64 [batch, n_q, heads * head_dim]: O = softmax(s Q K0^T + mask [causal]) V0 + w1[b] softmax(s Q K1^T) V1, per (batch item, head) and
+    query chunk so that self-attention at n = 9216 fits.  ``mask``: a contiguous [Bm, Hm, Qm, len0] tensor as ``ops.attention`` takes it, or a
+    pointer with ``mask_bs`` / ``mask_hs`` / ``mask_qs`` (the descriptor's fields); ``w1_dev``: one float or, with ``ip_scale_count`` = batch
+    (tg_attention_ps), one per batch item; causal and mask both apply when both are set"""
     B, H, D, nq = int(a["batch"]), int(a["heads"]), int(a["head_dim"]), int(a["n_q"])
     HD = H * D
     regs = {r.name: r for r in attention_read_extents(a)}
     scale = float(a["scale"])
-    w1 = float(a["w1_dev"].reshape(-1)[0].item()) if a.get("w1_dev") is not None else float(a.get("w1") or 0.0)
-    mask = a.get("mask")
+    if a.get("w1_dev") is not None and "w1_dev" in regs:
+        w1s = [float(v) for v in regs["w1_dev"].view().tolist()]                  # one float, or one per batch item (tg_attention_ps)
+        w1s = w1s if len(w1s) > 1 else w1s * B
+    else:
+        w1s = [float(a.get("w1") or 0.0)] * B
+    mask = None
+    if a.get("mask") is not None:
+        mask = _rd(a["mask"], 0, (B, H, nq, int(a["len0"])), attention_mask_strides(a) + (1,))     # broadcast by the zero strides
     q_all = regs["q"].view()
     out = torch.empty((B, nq, HD), dtype=torch.float64, device=q_all.device)
     segs = [s for s in ("0", "1") if int(a["len" + s]) > 0]
@@ -336,11 +363,9 @@ def attention_reference(q_chunk=2048, **a):
                     vt = kv[s][1][b, cs, :].to(torch.float64)[None]
                     bias = None
                     if s == "0" and mask is not None:
-                        bm, hm, qm, _ = mask.shape
-                        mrow = mask[b if bm > 1 else 0, h if hm > 1 else 0]
-                        bias = (mrow[i0:i1] if qm > 1 else mrow).to(torch.float64)[None]
-                    o = _segment(q, k, vt, scale, bias, bool(a.get("causal")) and s == "0", i0)
-                    acc = acc + (o if s == "0" else w1 * o)
+                        bias = mask[b, h, i0:i1].to(torch.float64)[None]
+                    o = _segment(q, k, vt, scale, bias, bool(a.get("causal")) and s == "0", i0)     # causal and mask: both apply
+                    acc = acc + (o if s == "0" else w1s[b] * o)
                 out[b, i0:i1, cs] = acc[0]
     return out
 

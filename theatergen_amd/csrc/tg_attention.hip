@@ -287,7 +287,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
     } else {
       if (__any(tm * p.scale_log2 > m_run * p.scale_log2 + LAZY_LOG2)) {
         const float m_new = fmaxf(m_run, tm);
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);
+        // MASK: a row that has seen no visible key yet (every key of its tiles so far masked with -inf, or with a value whose mask / scale overflows
+        // to it) takes this branch with the wave while m_run = m_new = -inf: its accumulators are zero and stay so, never exp2(-inf + inf)
+        const float alpha = (MASK && m_new == -INFINITY) ? 1.0f : __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);
 #pragma unroll
         for (int t2 = 0; t2 < DT; ++t2)
 #pragma unroll
@@ -295,7 +297,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DV <= 64 ? 
         if (!ONES) l_run *= alpha;
         m_run = m_new;
       }
-      mc = m_run * p.scale_log2;
+      // MASK: while no visible key has been seen the reference is 0 (tg_attention_wide_kmask's rule): exp2(fma(-inf, c, -0)) = 0 exactly
+      mc = (MASK && m_run == -INFINITY) ? 0.f : m_run * p.scale_log2;
+      if constexpr (MASK) {
+        // a row whose every key so far carries a huge finite mask (-1e30: the reference is the mask itself): fma(x, c, -mc) leaves the rounding
+        // error of mc = m_run * c, 2^-24 |mc|, as exp2's argument — a per-row constant that softmax forgives until it leaves exp2's range (+-inf
+        // or 0 for every key of the row: NaN).  From |mc| = 2^24 on the argument is formed as (x - m_run) * c instead: x - 0 and c * 0 keep the
+        // bits of every row below that
+        const float far = __builtin_fabsf(mc) >= 16777216.f ? m_run : 0.f;
+#pragma unroll
+        for (int kvt = 0; kvt < 2; ++kvt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[kvt][r] -= far;
+        mc = far != 0.f ? 0.f : mc;
+      }
     }
     // exp2 of one score register: FOLD scores are exp2's argument already
     auto ex = [&](float x) { return FOLD ? __builtin_amdgcn_exp2f(x) : __builtin_amdgcn_exp2f(__builtin_fmaf(x, p.scale_log2, -mc)); };
@@ -472,6 +487,22 @@ extern "C" int tg_attention_ps(const tg_attn_desc* d, int32_t ip_scale_count, vo
            "tg_attention: pitches must keep 16-byte alignment");
   TG_CHECK(d->len1 >= 0 && d->len1 <= KV, TG_ERR_ARG, "tg_attention: len1 (%d) must be <= 64", d->len1);
   if (d->len1 > 0) TG_CHECK(d->k1 && d->vt1 && d->k1_ld % 8 == 0 && d->vt1_ld % 8 == 0, TG_ERR_ARG, "tg_attention: bad segment 1");
+  // the lazy running max and the mask's 1 / scale assume c = scale * log2(e) > 0 (!(x > 0) also refuses NaN)
+  TG_CHECK(d->scale > 0.f, TG_ERR_ARG, "tg_attention: scale must be > 0");
+  // every K / V^T request is a 16-byte LDS-DMA, a Q fragment a 16-byte load, an output store 8 bytes, a mask element 4
+  auto misaligned = [](const void* ptr, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(ptr) & (bytes - 1)) != 0; };
+  TG_CHECK(!misaligned(d->q, 16) && !misaligned(d->k0, 16) && !misaligned(d->vt0, 16) && !misaligned(d->out, 8), TG_ERR_ARG,
+           "tg_attention: q, k0 and vt0 must be 16-byte aligned, out 8-byte");
+  TG_CHECK(d->vt0_ld >= d->len0, TG_ERR_ARG, "tg_attention: vt0_ld (%lld) must cover len0 (%d)", (long long)d->vt0_ld, d->len0);
+  if (d->len1 > 0) {
+    TG_CHECK(!misaligned(d->k1, 16) && !misaligned(d->vt1, 16), TG_ERR_ARG, "tg_attention: k1 and vt1 must be 16-byte aligned");
+    TG_CHECK(d->vt1_ld >= d->len1, TG_ERR_ARG, "tg_attention: vt1_ld (%lld) must cover len1 (%d)", (long long)d->vt1_ld, d->len1);
+  }
+  TG_CHECK(d->mask == nullptr || !misaligned(d->mask, 4), TG_ERR_ARG, "tg_attention: mask must be 4-byte aligned");
+  TG_CHECK(d->batch == 1 || (d->q_bs % 8 == 0 && d->k0_bs % 8 == 0 && d->vt0_bs % 8 == 0 && d->out_bs % 4 == 0), TG_ERR_ARG,
+           "tg_attention: batch strides must keep 16-byte alignment (q_bs, k0_bs, vt0_bs multiples of 8, out_bs of 4)");
+  TG_CHECK(d->batch == 1 || d->len1 == 0 || (d->k1_bs % 8 == 0 && d->vt1_bs % 8 == 0), TG_ERR_ARG,
+           "tg_attention: segment 1's batch strides must keep 16-byte alignment (k1_bs, vt1_bs multiples of 8)");
   TG_CHECK(ip_scale_count == 0 || ip_scale_count == 1 || ip_scale_count == d->batch, TG_ERR_ARG,
            "tg_attention_ps: ip_scale_count = %d (0 or 1: w1_dev is one float; batch = %d: one per batch item)", ip_scale_count, d->batch);
   TG_CHECK(ip_scale_count <= 1 || d->w1_dev != nullptr, TG_ERR_ARG, "tg_attention_ps: ip_scale_count = %d needs w1_dev", ip_scale_count);
@@ -487,7 +518,6 @@ extern "C" int tg_attention_ps(const tg_attn_desc* d, int32_t ip_scale_count, vo
   p.out = d->out; p.out_ld = d->out_ld; p.out_bs = d->out_bs;
   p.causal = d->causal;
   if (d->mask != nullptr) {
-    TG_CHECK(d->scale > 0.f, TG_ERR_ARG, "tg_attention: an additive mask needs scale > 0");
     p.mask = d->mask; p.mask_bs = d->mask_bs; p.mask_hs = d->mask_hs; p.mask_qs = d->mask_qs;
     p.inv_scale = 1.0f / d->scale;
   }

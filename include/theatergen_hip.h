@@ -1037,6 +1037,50 @@ int tg_sam_mask_head(int32_t dtype, const void* x, int32_t images, int32_t g, co
 int tg_sam_mask_post(const float* logits, int32_t planes, int32_t L, int32_t S, int32_t hr, int32_t wr, int32_t h0, int32_t w0, float threshold,
                      int32_t ht, int32_t wt, uint8_t* mask, int32_t* areas, void* stream);
 
+/* GroundingDINO's decoder head pieces that are not GEMMs, attention or LayerNorm (csrc/tg_dino_head.hip).  Additive to ABI 308: two new symbols, no
+ * descriptor, TG_ABI_VERSION unchanged.  In both, every output element is written by exactly one lane, no atomics, no workspace: equal inputs give equal
+ * bits, and a batch item's outputs do not depend on the batch.  Both refuse on the host before any launch, writing nothing, with tg_last_error() set.
+ *
+ * tg_dino_contrastive: transformers' GroundingDinoContrastiveEmbedding without its tensor.
+ *   q           [batch][n][d], model dtype, row pitch q_ld and batch pitch q_bs (elements).
+ *   text        [batch][text_len][d], model dtype, row pitch t_ld, batch pitch t_bs.  Rows at or past text_len and columns at or past d are never read.
+ *   token_mask  uint8, dense [batch][text_len], 1 = real token.
+ *   logits      optional fp32, dense [batch][n][max_text_len]: q_bq . text_bt for a real token t < text_len, -inf for a masked token and for the columns
+ *               text_len .. max_text_len - 1 (what transformers returns).
+ *   row_max     optional fp32, dense [batch][n]: the maximum over the real tokens, -inf if there are none; bit-equal to the maximum of the row of
+ *               logits the same call writes (finite operands: fmaxf drops a NaN product).
+ * The products are 32 x 32 x 16 MFMAs on the stored operands with fp32 accumulation, a masked token's product is discarded after it was computed (NaN in
+ * a masked row reaches nothing).  One wave per 32 queries.  Instances: d 128 / 256, bf16 and fp16, no LDS, no scratch.
+ *   TG_ERR_UNSUPPORTED  d not 128 or 256; not 1 <= text_len <= max_text_len <= 256.
+ *   TG_ERR_ARG          bad dtype; batch or n < 1; a null q / text / token_mask; neither logits nor row_max; q_ld / t_ld not multiples of 8 or < d; with
+ *                       batch > 1 q_bs / t_bs negative or not multiples of 8; q or text not 16-byte aligned, logits or row_max not 4-byte aligned.
+ *
+ * tg_dino_box_update: the tail of every box step of the decoder, which carries the reference boxes in fp32.  Per row (one query; rows = batch *
+ * rows_per_batch, the batch item of a row is row / rows_per_batch):
+ *   h             [rows][d], model dtype, row pitch h_ld: the output of the box MLP's second layer after ReLU.
+ *   w3, b3        the MLP's last layer: w3 [4][d] model dtype, dense; b3 fp32 [4].
+ *   prior         fp32, dense [rows][4].  prior_is_box 0: logits used as they are (+inf allowed: the encoder proposals); prior_is_box 1: boxes whose
+ *                 torch.special.logit(x, eps = 1e-5) = log(c / (1 - c)), c = clamp(x, 1e-5, 1 - 1e-5), is taken here in fp32.
+ *   valid_ratios  fp32, dense [batch][n_levels][2] = (x, y); needed with ref_levels or pos_in.
+ *   ref           fp32, dense [rows][4] = sigmoid((h . w3_c + b3_c) + prior_c), sigmoid(t) = 1 / (1 + exp(-t)): +inf gives exactly 1.  The dot product is
+ *                 fp32 FMAs on the stored operands, d / 64 per lane, then a butterfly sum over the 64 lanes.
+ *   ref_levels    optional fp32, dense [rows][n_levels][4] = ref * (vr_x, vr_y, vr_x, vr_y) of the level: the ref operand of tg_msdeform_attn, ref_dim 4.
+ *   pos_in        optional [rows][2 d], model dtype, row pitch pos_ld: transformers' encode_sinusoidal_position_embedding(ref_levels[:, 0], d / 2).  Four
+ *                 blocks of d / 2 channels for the coordinates (y, x, w, h) (x and y swapped, as there); channel 2 m of a block is sin(a), 2 m + 1 is
+ *                 cos(a), a = 2 pi c / 10000^(4 m / d).  fp32: the argument is reduced in turns (t - rint(t), exact) before the precise sinf / cosf, the
+ *                 result rounded once.
+ * One wave per row.  Instances: d 128 / 256, bf16 and fp16, no LDS, no scratch.
+ *   TG_ERR_UNSUPPORTED  d not 128 or 256; with ref_levels or pos_in, n_levels outside 1 .. 4.
+ *   TG_ERR_ARG          bad dtype; rows < 1 or >= 2^31, rows_per_batch < 1 or not a divisor of rows; prior_is_box not 0 / 1; a null h / w3 / b3 / prior /
+ *                       ref; ref_levels or pos_in without valid_ratios; h_ld < d; pos_ld < 2 d; prior not 16-byte aligned, another fp32 operand not
+ *                       4-byte aligned, h / w3 / pos_in not 2-byte aligned. */
+int tg_dino_contrastive(int32_t dtype, int32_t batch, int32_t n, int32_t d, int32_t text_len, int32_t max_text_len, const void* q, int64_t q_ld,
+                        int64_t q_bs, const void* text, int64_t t_ld, int64_t t_bs, const uint8_t* token_mask, float* logits, float* row_max,
+                        void* stream);
+int tg_dino_box_update(int32_t dtype, int64_t rows, int32_t rows_per_batch, int32_t d, const void* h, int64_t h_ld, const void* w3, const float* b3,
+                       const float* prior, int32_t prior_is_box, const float* valid_ratios, int32_t n_levels, float* ref, float* ref_levels,
+                       void* pos_in, int64_t pos_ld, void* stream);
+
 /* debugging aid: raw 32x32x16 MFMA on caller-provided fragments (64 lanes x 8 elements each) */
 int tg_debug_mfma32(int32_t dtype, const void* a_frags, const void* b_frags, float* d_out, void* stream);
 

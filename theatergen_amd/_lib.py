@@ -217,6 +217,8 @@ SIGNATURES = {
     "tg_xq_attn_ps": (i32, [C.POINTER(XqAttnDesc), i32, vp]),
     "tg_xq_kv_bytes": (i64, [i32, i32, i32]),
     "tg_xq_kv_pack": (i32, [i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp]),
+    "tg_dino_contrastive": (i32, [i32, i32, i32, i32, i32, i32, vp, i64, i64, vp, i64, i64, vp, vp, vp, vp]),
+    "tg_dino_box_update": (i32, [i32, i64, i32, i32, vp, i64, vp, vp, vp, i32, vp, i32, vp, vp, vp, i64, vp]),
     "tg_debug_mfma32": (i32, [i32, vp, vp, vp, vp]),
 }
 

@@ -149,6 +149,12 @@ HOT_GATES = [
     ("sam_mask_head_kernel<", 0, 128),
     ("sam_posenc_kernel<", 0, 64),
     ("sam_mask_post_kernel", 0, 96),
+    # GroundingDINO's decoder head (tg_dino_head.hip).  The contrastive kernel (<T, KS>) keeps the wave's query fragments (KS = d / 16 registers of 8
+    # elements: 32 / 64 VGPRs) and one 16-register accumulator with compile-time indices (scratch = one of them was indexed at run time); 70 / 102 VGPRs
+    # as built, four waves per SIMD at d = 256.  The box update (<T, D>) calls the precise logf / expf / powf / sinf / cosf on small arguments (scratch =
+    # the large-argument path's tables came back); 25 .. 34 VGPRs as built
+    ("dino_contrastive_kernel<", 0, 102),
+    ("dino_box_update_kernel<", 0, 34),
     ("attention_wide_combine_kernel<", 0, 64),
     # the key-padding-mask instances of the two kernels around this entry (tg_attention_wide_kmask; <T, D, DO, SPLIT> / <T, D>): the same bodies with a KMASK flag, kernels of
     # their own names so that the unmasked instances keep theirs; the same budgets for the same reasons (the mask is two 8-byte loads per lane and tile)

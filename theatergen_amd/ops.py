@@ -673,6 +673,115 @@ def msdeform_attn(value, v_ld, v_bs, shapes, offsets, off_ld, logits, log_ld, re
     return out
 
 
+def dino_contrastive(q, text, token_mask, max_text_len, logits=True, row_max=False):
+    """``tg_dino_contrastive``: transformers' GroundingDinoContrastiveEmbedding.  ``q`` [batch, n, d] and ``text`` [batch, Lt, d] in the storage dtype, unit
+    stride along d, any row / batch pitch that is a multiple of 8 (views of wider buffers are taken as they are); ``token_mask`` [batch, Lt] bool / uint8,
+    1 = real token.  ``logits`` / ``row_max``: True allocates, a tensor is written, False / None leaves the output out; at least one.
+    -> (logits fp32 [batch, n, max_text_len] or None, row_max fp32 [batch, n] or None).  The arguments are checked before the device is."""
+    for name, t in (("q", q), ("text", text)):
+        if not torch.is_tensor(t) or t.ndim != 3 or t.stride(2) != 1:
+            raise RuntimeError(f"dino_contrastive: {name} must be a [batch, rows, d] tensor with unit stride along d")
+    dt = _dt(q)
+    B, n, d = (int(v) for v in q.shape)
+    Lt, mtl = int(text.shape[1]), int(max_text_len)
+    if text.dtype != q.dtype or text.device != q.device or text.shape[0] != B or text.shape[2] != d:
+        raise RuntimeError(f"dino_contrastive: text {tuple(text.shape)} {text.dtype} does not match q {tuple(q.shape)} {q.dtype}")
+    if B < 1 or n < 1:
+        raise RuntimeError(f"dino_contrastive: empty problem (batch {B}, n {n})")
+    if d not in (128, 256):
+        raise RuntimeError(f"dino_contrastive: d = {d} unsupported (128 or 256)")
+    if not 1 <= Lt <= mtl <= 256:
+        raise RuntimeError(f"dino_contrastive: text_len {Lt} / max_text_len {mtl} unsupported (1 <= text_len <= max_text_len <= 256)")
+    if tuple(token_mask.shape) != (B, Lt) or token_mask.dtype not in (torch.bool, torch.uint8) or token_mask.device != q.device:
+        raise RuntimeError(f"dino_contrastive: token_mask must be a bool / uint8 tensor [{B}, {Lt}] on {q.device}, got {tuple(token_mask.shape)} "
+                           f"{token_mask.dtype}")
+    for name, t in (("q", q), ("text", text)):
+        if t.stride(1) % 8 or t.stride(1) < d or (B > 1 and (t.stride(0) % 8 or t.stride(0) < 0)) or t.data_ptr() % 16:
+            raise RuntimeError(f"dino_contrastive: {name} pitches (row {t.stride(1)}, batch {t.stride(0)}) must be multiples of 8 covering d, its base "
+                               "16-byte aligned")
+    if (logits is None or logits is False) and (row_max is None or row_max is False):
+        raise RuntimeError("dino_contrastive: neither logits nor row_max asked for")
+    outs = []
+    for name, o, shape in (("logits", logits, (B, n, mtl)), ("row_max", row_max, (B, n))):
+        if o is None or o is False:
+            outs.append(None)
+        elif o is True:
+            outs.append(torch.empty(shape, dtype=torch.float32, device=q.device))
+        else:
+            if not torch.is_tensor(o) or o.dtype != torch.float32 or tuple(o.shape) != shape or not o.is_contiguous() or o.device != q.device:
+                raise RuntimeError(f"dino_contrastive: {name} must be a contiguous fp32 tensor {shape} on {q.device}")
+            outs.append(o)
+    _need_cuda(q)
+    mask = token_mask.to(torch.uint8).contiguous() if token_mask.dtype != torch.uint8 or not token_mask.is_contiguous() else token_mask
+    _lib.check(_lib.lib().tg_dino_contrastive(dt, B, n, d, Lt, mtl, _ptr(q), int(q.stride(1)), int(q.stride(0)), _ptr(text), int(text.stride(1)),
+                                              int(text.stride(0)), _ptr(mask), _ptr(outs[0]), _ptr(outs[1]), _stream()))
+    return outs[0], outs[1]
+
+
+def dino_box_update(h, w3, b3, prior, prior_is_box, rows_per_batch=None, valid_ratios=None, ref=None, ref_levels=False, pos_in=False):
+    """``tg_dino_box_update``: ``h`` [rows, d] storage dtype (unit stride along d; the box MLP's second layer after ReLU), ``w3`` [4, d] storage dtype, ``b3``
+    fp32 [4], ``prior`` fp32 [rows, 4] — logits (``prior_is_box`` False, +inf allowed) or boxes whose logit(eps = 1e-5) the kernel takes (True);
+    ``valid_ratios`` fp32 [batch, L, 2] with rows = batch * ``rows_per_batch``.  ``ref_levels`` / ``pos_in``: True allocates, a tensor is written, False
+    leaves it out.  -> (ref fp32 [rows, 4], ref_levels fp32 [rows, L, 4] or None, pos_in [rows, 2 d] storage dtype or None).  The arguments are checked
+    before the device is."""
+    if not torch.is_tensor(h) or h.ndim != 2 or h.stride(1) != 1:
+        raise RuntimeError("dino_box_update: h must be a [rows, d] tensor with unit stride along d")
+    dt = _dt(h)
+    rows, d = int(h.shape[0]), int(h.shape[1])
+    dev = h.device
+    if rows < 1:
+        raise RuntimeError("dino_box_update: empty problem (rows 0)")
+    if d not in (128, 256):
+        raise RuntimeError(f"dino_box_update: d = {d} unsupported (128 or 256)")
+    if h.stride(0) < d:
+        raise RuntimeError(f"dino_box_update: h row pitch {h.stride(0)} does not cover d = {d}")
+    if w3.dtype != h.dtype or tuple(w3.shape) != (4, d) or not w3.is_contiguous() or w3.device != dev:
+        raise RuntimeError(f"dino_box_update: w3 must be a contiguous {h.dtype} tensor [4, {d}] on {dev}, got {tuple(w3.shape)} {w3.dtype}")
+
+    def f32(t, shape, what):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError(f"dino_box_update: {what} must be a contiguous fp32 tensor {shape} on {dev}")
+    f32(b3, (4,), "b3")
+    f32(prior, (rows, 4), "prior")
+    if prior.data_ptr() % 16:
+        raise RuntimeError("dino_box_update: prior must be 16-byte aligned")
+    want_levels, want_pos = ref_levels is not None and ref_levels is not False, pos_in is not None and pos_in is not False
+    L = 0
+    rpb = rows if rows_per_batch is None else int(rows_per_batch)
+    if rpb < 1 or rows % rpb:
+        raise RuntimeError(f"dino_box_update: rows = {rows} must be a multiple of rows_per_batch = {rpb}")
+    if want_levels or want_pos:
+        if valid_ratios is None:
+            raise RuntimeError("dino_box_update: ref_levels / pos_in need valid_ratios")
+        if not torch.is_tensor(valid_ratios) or valid_ratios.ndim != 3 or not 1 <= int(valid_ratios.shape[1]) <= 4:
+            raise RuntimeError("dino_box_update: valid_ratios must be [batch, L, 2] with 1 <= L <= 4")
+        L = int(valid_ratios.shape[1])
+        f32(valid_ratios, (rows // rpb, L, 2), "valid_ratios")
+    if ref is None:
+        ref = torch.empty((rows, 4), dtype=torch.float32, device=dev)
+    else:
+        f32(ref, (rows, 4), "ref")
+    if ref_levels is True:
+        ref_levels = torch.empty((rows, L, 4), dtype=torch.float32, device=dev)
+    elif want_levels:
+        f32(ref_levels, (rows, L, 4), "ref_levels")
+    else:
+        ref_levels = None
+    if pos_in is True:
+        pos_in = torch.empty((rows, 2 * d), dtype=h.dtype, device=dev)
+    elif want_pos:
+        if not torch.is_tensor(pos_in) or pos_in.dtype != h.dtype or tuple(pos_in.shape) != (rows, 2 * d) or pos_in.stride(1) != 1 or \
+                pos_in.stride(0) < 2 * d or pos_in.device != dev:
+            raise RuntimeError(f"dino_box_update: pos_in must be a {h.dtype} tensor [{rows}, {2 * d}] on {dev} with unit stride along the channels")
+    else:
+        pos_in = None
+    _need_cuda(h)
+    _lib.check(_lib.lib().tg_dino_box_update(dt, rows, rpb, d, _ptr(h), int(h.stride(0)), _ptr(w3), _ptr(b3), _ptr(prior), 1 if prior_is_box else 0,
+                                             _ptr(valid_ratios) if L else None, L, _ptr(ref), _ptr(ref_levels), _ptr(pos_in),
+                                             int(pos_in.stride(0)) if pos_in is not None else 0, _stream()))
+    return ref, ref_levels, pos_in
+
+
 def _f32_dev(t, what, numel=None):
     _need_cuda(t)
     if t.dtype != torch.float32 or not t.is_contiguous() or (numel is not None and t.numel() != numel):

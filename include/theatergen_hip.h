@@ -780,6 +780,36 @@ int tg_image_from_u8(const void* src, int32_t batch, int32_t h, int32_t w, int32
 int tg_image_to_u8(const void* src, int32_t src_dtype, int32_t batch, int32_t h, int32_t w, void* dst, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Image preprocessing (csrc/tg_image_resample.hip): what a `transformers` image processor does to a uint8 RGB image — PIL resize, * rescale_factor,
+ * (x - mean) / std, zero padding, CHW — in one launch, bit-equal to the processor.  Additive to ABI 308: one new symbol, TG_ABI_VERSION unchanged.
+ *
+ * tg_image_resample_u8: src uint8 [batch, hs, ws, 3] -> dst NCHW [batch, 3, hp, wp] in dst_dtype (TG_BF16, TG_F16 or 2 = fp32).
+ *   Per axis (v: hs -> rh rows, h: ws -> rw columns) the host brings Pillow's 8-bit coefficient tables, on the device: k int32 [out][ksize] with 22
+ *   fractional bits, first int32 [out], count int32 [out] (theatergen_amd/preprocess.py: resample_plan; 255 * sum |k| + 2^21 < 2^31 per row, so
+ *   int32 accumulation is exact).  A pass is (2^21 + sum_t p[first + t] * k[t]) >> 22 (arithmetic shift), clipped to 0 .. 255.  The HORIZONTAL pass runs
+ *   first and rounds to uint8, then the vertical pass: Pillow's order, Pillow's bytes.  An identity axis is one coefficient 2^22.
+ *   The output window is rows oy .. oy + oh, columns ox .. ox + ow of the [rh, rw] resized image (a centre crop; otherwise origin 0 and the full size).
+ *   Per window pixel and channel c: value = lut[c * 256 + byte] (lut fp32 [3][256]: the processor's rescale + normalise of every byte, made on the
+ *   host), rounded ONCE to dst_dtype.  Every dst element at a row >= oh or a column >= ow is +0.  u8_out (or NULL): uint8 [batch, oh, ow, 3], the
+ *   resized bytes of the window.  One lane writes each element, no atomics; an image's output does not depend on the batch.  No host
+ *   synchronisation: with device-resident tables the call can be captured in a graph.
+ *   Routes.  tmp == NULL: ONE launch; a workgroup owns TG_RESAMPLE_TILE_H x TG_RESAMPLE_TILE_W window pixels and stages the horizontally resampled
+ *   source rows its vertical taps reach in LDS.  stage_rows = the largest number of such rows over the window's tiles (rows ty .. ty + TILE_H - 1
+ *   of the window: first_v[oy + last] + count_v[oy + last] - first_v[oy + ty]); it must satisfy stage_rows * TILE_W * 3 <= TG_RESAMPLE_LDS_BYTES.
+ *   tmp != NULL (strong vertical downscales): TWO launches through tmp, uint8 [batch, hs, ow, 3]; stage_rows is ignored.  Same bytes either way.
+ *   TG_ERR_ARG before any launch, nothing written: a null src / dst / lut / table; batch or a size < 1 or > TG_RESAMPLE_MAX_SIZE; ksize < 1; a
+ *   window outside the resized image; hp < oh or wp < ow; a bad dtype; src == dst (or u8_out / tmp equal to either); tmp == NULL with a
+ *   stage_rows outside 1 .. TG_RESAMPLE_LDS_BYTES / (3 * TG_RESAMPLE_TILE_W). */
+#define TG_RESAMPLE_TILE_H 16
+#define TG_RESAMPLE_TILE_W 128
+#define TG_RESAMPLE_LDS_BYTES 20480
+#define TG_RESAMPLE_MAX_SIZE 8192
+int tg_image_resample_u8(const void* src, int32_t batch, int32_t hs, int32_t ws, const int32_t* kv, const int32_t* first_v, const int32_t* count_v,
+                         int32_t ksize_v, int32_t rh, const int32_t* kh, const int32_t* first_h, const int32_t* count_h, int32_t ksize_h, int32_t rw,
+                         int32_t oy, int32_t ox, int32_t oh, int32_t ow, const float* lut, void* dst, int32_t dst_dtype, int32_t hp, int32_t wp,
+                         void* u8_out, int32_t stage_rows, void* tmp, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-box guidance reductions (utils/guidance.py:91-148, 223-233) on an attention map
  * attn fp32 [heads, hw, n_tok]; mask fp32 [hw] (box mask).  One (token) column per call-row:
  * tg_guidance_topk: for each head: fg = mean(topk_{k_fg}(A*M)), bg = mean(topk_{k_bg}(A*(1-M)));

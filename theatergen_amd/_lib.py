@@ -15,6 +15,8 @@ TG_BF16, TG_F16 = 0, 1
 ABI_VERSION = 308          # TG_ABI_VERSION of include/theatergen_hip.h this binding was written against
 ACT_NONE, ACT_SILU, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2, 3
 RC_FF_TWO_WAVE = 0x10000     # TG_RC_FF_TWO_WAVE: kernel selector bit in the `dbg` word of tg_rc_ff_desc
+# TG_RESAMPLE_TILE_H / _TILE_W / _LDS_BYTES / _MAX_SIZE: the fused tile of tg_image_resample_u8 and its LDS budget (the host plan picks the route with them)
+RESAMPLE_TILE_H, RESAMPLE_TILE_W, RESAMPLE_LDS_BYTES, RESAMPLE_MAX_SIZE = 16, 128, 20480, 8192
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -194,6 +196,7 @@ SIGNATURES = {
     "tg_add_noise": (i32, [vp, vp, vp, vp, i32, i64, vp, vp]),
     "tg_image_from_u8": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, vp]),
     "tg_image_to_u8": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    "tg_image_resample_u8": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, i32, vp, vp]),
     "tg_guidance_topk": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, f32, f32, f32, vp, vp, vp]),
     "tg_guidance_ratio": (i32, [vp, i32, i32, i32, i32, vp, f32, vp, vp, vp]),
     "tg_guidance_ref": (i32, [vp, i32, i32, i32, i32, vp, vp, f32, f32, vp, vp, vp]),

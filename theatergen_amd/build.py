@@ -196,6 +196,11 @@ HOT_GATES = [
     # per-thread value arrays were indexed at run time
     ("image_from_u8_kernel<", 0, 64),
     ("image_to_u8_kernel<", 0, 64),
+    # Pillow-exact resize + normalise + pad (tg_image_resample.hip; fused <T>, the two-launch pair): integer accumulators and three bytes per thread —
+    # scratch would mean the per-pixel channel array was indexed at run time.  64 VGPRs keeps the eight workgroups per CU the LDS budget is sized for
+    ("image_resample_fused_kernel<", 0, 64),
+    ("image_resample_h_kernel", 0, 64),
+    ("image_resample_v_kernel<", 0, 64),
 ]
 
 

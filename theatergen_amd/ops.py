@@ -1367,6 +1367,63 @@ def image_to_u8(images, out=None):
     return out
 
 
+resample_launches = {"fused": 0, "two_launch": 0}            # calls of image_resample_u8 by route (tests and timing scripts read it)
+
+
+def image_resample_u8(images, plan_v, plan_h, lut, dtype, window=None, pad=None, out=None, u8_out=None, route=None):
+    """uint8 RGB ``[B, hs, ws, 3]`` on the device -> ``pixel_values`` NCHW ``[B, 3, hp, wp]`` in ``dtype`` (bf16 / fp16 / fp32): Pillow's 8-bit resize
+    (horizontal pass first, each pass rounded to uint8), ``lut[c][byte]`` (fp32 ``[3, 256]``, the processor's rescale + normalise), one rounding to
+    ``dtype``, +0 outside the window.  ``plan_v`` / ``plan_h``: ``preprocess.device_plan(hs, rh, filter, device)`` / ``(ws, rw, ...)``.
+    ``window`` = (oy, ox, oh, ow) inside the resized image (default: all of it); ``pad`` = (hp, wp) (default: the window, or ``out``'s shape).
+    ``u8_out``: a uint8 ``[B, oh, ow, 3]`` tensor, or True to allocate one; returned as the second value.  ``route``: None lets the plan decide
+    (``preprocess.resample_route``), "fused" / "two_launch" force one; both give the same bytes.  See tg_image_resample_u8 in include/theatergen_hip.h."""
+    from . import preprocess
+    _need_cuda(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+        raise ValueError(f"image_resample_u8: uint8 [B, H, W, 3] expected, got {images.dtype} {tuple(images.shape)}")
+    if dtype not in _SRC:
+        raise RuntimeError(f"theatergen_amd: image_resample_u8 writes bf16 / fp16 / fp32, not {dtype}")
+    B, hs, ws, _ = (int(v) for v in images.shape)
+    (pv, kv, fv, cv), (ph, kh, fh, ch) = plan_v, plan_h
+    if (pv.in_size, ph.in_size) != (hs, ws):
+        raise ValueError(f"image_resample_u8: plans for {(pv.in_size, ph.in_size)} sources, images are {(hs, ws)}")
+    for t in (kv, fv, cv, kh, fh, ch, lut):
+        if not t.is_cuda or t.device != images.device or not t.is_contiguous():
+            raise ValueError("image_resample_u8: tables and lut must be contiguous tensors on the images' device")
+    if lut.dtype != torch.float32 or tuple(lut.shape) != (3, 256) or any(t.dtype != torch.int32 for t in (kv, fv, cv, kh, fh, ch)):
+        raise ValueError("image_resample_u8: lut fp32 [3, 256] and int32 tables expected")
+    rh, rw = pv.out_size, ph.out_size
+    oy, ox, oh, ow = (int(v) for v in (window if window is not None else (0, 0, rh, rw)))
+    if oy < 0 or ox < 0 or oh < 1 or ow < 1 or oy + oh > rh or ox + ow > rw:
+        raise ValueError(f"image_resample_u8: window {(oy, ox, oh, ow)} leaves the resized image {(rh, rw)}")
+    if pad is None:
+        pad = tuple(out.shape[-2:]) if out is not None else (oh, ow)
+    hp, wp = int(pad[0]), int(pad[1])
+    if hp < oh or wp < ow:
+        raise ValueError(f"image_resample_u8: pad {(hp, wp)} smaller than the window {(oh, ow)}")
+    images = images.contiguous()
+    if out is None:
+        out = torch.empty((B, 3, hp, wp), dtype=dtype, device=images.device)
+    elif tuple(out.shape) != (B, 3, hp, wp) or out.dtype != dtype or not out.is_contiguous() or out.device != images.device:
+        raise ValueError(f"image_resample_u8: out must be a contiguous {dtype} tensor of shape {(B, 3, hp, wp)} on the images' device")
+    if u8_out is True:
+        u8_out = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=images.device)
+    elif u8_out is not None and (tuple(u8_out.shape) != (B, oh, ow, 3) or u8_out.dtype != torch.uint8 or not u8_out.is_contiguous()
+                                 or u8_out.device != images.device):
+        raise ValueError(f"image_resample_u8: u8_out must be a contiguous uint8 tensor of shape {(B, oh, ow, 3)} on the images' device")
+    planned, rows = preprocess.resample_route(pv, oy, oh)
+    if route is None:
+        route = planned
+    elif route not in ("fused", "two_launch") or (route == "fused" and planned != "fused"):
+        raise ValueError(f"image_resample_u8: route {route!r} (the plan needs {rows} staged rows: {planned})")
+    tmp = workspace(B * hs * ow * 3, images.device) if route == "two_launch" else None
+    _lib.check(_lib.lib().tg_image_resample_u8(_ptr(images), B, hs, ws, _ptr(kv), _ptr(fv), _ptr(cv), int(kv.shape[1]), rh, _ptr(kh), _ptr(fh), _ptr(ch),
+                                               int(kh.shape[1]), rw, oy, ox, oh, ow, _ptr(lut), _ptr(out), _SRC[dtype], hp, wp, _ptr(u8_out), rows,
+                                               _ptr(tmp), _stream()))
+    resample_launches[route] += 1
+    return out if u8_out is None else (out, u8_out)
+
+
 def blend_latents(bg, fg, mask, ratio, sigma=1.0, storage_dtype=None):
     """fp32 in / out; ``storage_dtype`` torch.float16 / torch.bfloat16: reproduce the half-precision roundings of the
     reference expression (its latents are ``unet.dtype`` tensors)"""

@@ -925,10 +925,11 @@ int tg_rc_kv_pack(int32_t dtype, int32_t batch, const void* k, const void* vt, i
 /* tg_rc_ff: norm3 + FeedForward(GEGLU) + residual of a first-level BasicTransformerBlock (models/attention.py:226-236, 328-338), and with
  * `wpo` != NULL also Transformer2DModel.proj_out + its residual (models/transformer_2d.py:316-327), in one launch:
  *     h3 = net2(a * gelu(g)) + b2 + h,  [a | g] = proj(LayerNorm(h)) + b1;      out = wpo ? proj_out(h3) + b + res0 : h3
- * `w1` / `w2` / `b2`: theatergen_amd/rowchain.py::pack_ff (LayerNorm gamma / beta folded into proj; the kernel normalises the rows);
- * `wpo`: rc_pack_tiles stream of proj_out (+ bias).  `inner` = the hidden width (1280).  `dbg`: reserved, must be 0, but for one bit:
- * TG_RC_FF_TWO_WAVE selects the kernel that runs two waves per SIMD (one 8-wave workgroup per 128 tokens, 16 tokens per wave on 16x16x32 MFMAs):
- * `w1` / `w2` are then rowchain.py::pack_ff2 streams and `wpo` a pack_po2 stream (other fragment order, same sizes). */
+ * `w1` / `w2` / `b2`: theatergen_amd/rowchain.py::pack_ff2 (LayerNorm gamma / beta folded into proj; the kernel normalises the rows);
+ * `wpo`: rowchain.py::pack_po2 stream of proj_out (+ bias).  `inner` = the hidden width (1280).  The launch is rc_ff2_kernel: two waves per SIMD, one
+ * 8-wave workgroup per 128 tokens, 16 tokens per wave on 16x16x32 MFMAs.  `dbg` must equal TG_RC_FF_TWO_WAVE: the bit names the stream format
+ * (pack_ff2 / pack_po2).  0 was the format of the retired one-wave kernel (pack_ff / rc_pack_tiles streams: same sizes, other fragment order) and is
+ * refused with TG_ERR_ARG before any launch, as is every other value: such streams would give wrong rows, not an error. */
 #define TG_RC_FF_TWO_WAVE 0x10000
 typedef struct {
   int32_t dtype;

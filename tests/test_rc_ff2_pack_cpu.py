@@ -57,9 +57,6 @@ def test_pack_ff2_and_po2_streams_emulated(inner, dt):
     s1, s2, bb2 = rowchain.pack_ff2(w1, b1, gamma, beta, w2, b2)
     ns = inner // 32
     assert s1.numel() == ns * 41 * 1024 + 3072 and s2.numel() == ns * 20 * 1024
-    # same sizes as the one-wave streams: the kernels share descriptor, LDS stages and DMA pattern
-    o1, o2, _ = rowchain.pack_ff(w1, b1, gamma, beta, w2, b2)
-    assert o1.numel() == s1.numel() and o2.numel() == s2.numel()
 
     HN = _row_pieces(xn)
     out = [bb2.reshape(10, 4, 2, 4)[s, :, u][:, None, :].repeat(1, 16, 1) for s in range(10) for u in range(2)]     # tile t: [g, n, i] = b2[32 s + 8 g + 4 u + i]
@@ -101,21 +98,23 @@ def test_pack_ff2_and_po2_streams_emulated(inner, dt):
 
 
 def test_two_wave_kernel_is_the_default_and_switchable():
-    """``TG_RC_MODE`` bit 5 selects the two-wave kernel; the default has it, 15 is the one-wave kernel"""
+    """the header defines the stream-format tag ``TG_RC_FF_TWO_WAVE`` with the binding's value; every row-chain launch is on by default (``TG_RC_MODE``
+    bits 0 - 3; bit 5 chose between two kernels while there were two and is ignored)"""
     import os
     if "TG_RC_MODE" not in os.environ:
-        assert rowchain.MODE & 32 and rowchain.MODE & 15 == 15
+        assert rowchain.MODE & 15 == 15
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "theatergen_hip.h")).read()
     assert f"#define TG_RC_FF_TWO_WAVE 0x{rowchain.FF_TWO_WAVE:x}" in header
 
 
 def test_retired_switch_names_are_gone():
-    """the A/B arms that lost were deleted with their switches (profiles/retired_arms_findings.md): no source of the package names one any more"""
+    """the A/B arms that lost were deleted with their switches (profiles/retired_arms_findings.md, rc_ff_one_wave_retired_findings.md): no source of
+    the package names one any more.  The last three are literal strings with their bracket, so that ``pack_ff2`` and ``rc_ff2_kernel`` do not hit"""
     import glob
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     retired = ["TG_NO_GN_FUSE", "TG_NO_LN_FUSE", "TG_LN_MODE", "TG_LN_FF_MAX_ROWS", "TG_CONV_OUT_GN", "TG_FF_PAD", "TG_RESAMPLER_SIDE", "TG_CONV_IN_MFMA",
-               "TG_CONV_OUT_MFMA", "TG_ATTN_NOFOLD", "TG_ATTN_PIPE", "TG_RC_DEV", "TG_RC_DEV_BUILD"]
+               "TG_CONV_OUT_MFMA", "TG_ATTN_NOFOLD", "TG_ATTN_PIPE", "TG_RC_DEV", "TG_RC_DEV_BUILD", "pack_ff(", "rc_ff_kernel<", "two_wave="]
     files = (glob.glob(os.path.join(root, "theatergen_amd", "**", "*.py"), recursive=True) + glob.glob(os.path.join(root, "theatergen_amd", "csrc", "*"))
              + glob.glob(os.path.join(root, "include", "*")))
     files = [f for f in files if os.path.isfile(f)]

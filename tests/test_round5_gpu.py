@@ -218,11 +218,12 @@ def test_ip_scale_assignment_is_fenced_against_engine_streams():
             assert torch.equal(seq[k], par[k]), f"gated concurrent replay differs from the gated single-stream run (engine {k}, repeat {rep})"
 
 
-def test_row_chain_dev_switches_are_rejected_in_release_calls():
+def test_row_chain_dev_switches_are_rejected_in_release_calls(monkeypatch):
     """the timing switches of the row-chain kernels (skip stores / barriers / MFMAs) rode in descriptor bits.  The switches are gone and the
     words they rode in are reserved: a descriptor that sets one is an argument error raised before any launch (the sentinel outputs stay untouched),
-    not a silently wrong result"""
-    from theatergen_amd import ops
+    not a silently wrong result.  ``tg_rc_ff``'s ``dbg`` word must hold the stream-format tag TG_RC_FF_TWO_WAVE: 0, the format of the retired one-wave
+    kernel, is refused in the same way"""
+    from theatergen_amd import _lib, ops
     from theatergen_amd.weights_pack import rc_pack
     bf = torch.bfloat16
     x = torch.randn(256, 320, device=DEV).to(bf)
@@ -245,6 +246,10 @@ def test_row_chain_dev_switches_are_rejected_in_release_calls():
         ops.rc_front(h, coef, tiles(10), tiles(30), 128, 1e-5, y=y, qk=qk, vt=vt, _reserved=256)
     with pytest.raises(RuntimeError):
         ops.rc_ff(h, u8(2 * 41 * 1024 + 3072), u8(2 * 20 * 1024), torch.zeros(320, device=DEV), 64, 1e-5, out=out, _reserved=1)
+    with monkeypatch.context() as m:
+        m.setattr(_lib, "RC_FF_TWO_WAVE", 0)              # the wrapper always sets the tag: dbg == 0 is reachable only without it
+        with pytest.raises(RuntimeError, match="retired"):
+            ops.rc_ff(h, u8(2 * 41 * 1024 + 3072), u8(2 * 20 * 1024), torch.zeros(320, device=DEV), 64, 1e-5, out=out)
     with pytest.raises(RuntimeError):
         ops.rc_xattn(h, tiles(10), kv, tiles(10), 128, 1e-5, 4, out=out, text_len=77 + 256)
     torch.cuda.synchronize()

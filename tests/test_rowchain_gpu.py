@@ -178,8 +178,8 @@ def test_first_level_block_row_chain_on_vs_off(dtype, ip, monkeypatch):
 def test_rc_ff_vs_fp32_reference(dtype, M, inner, proj):
     """norm3 + GEGLU feed-forward + residual (+ proj_out + residual) in one launch vs the fp32 restatement of models/attention.py:226-236,
     328-338 (erf GELU) and models/transformer_2d.py:316-327"""
+    from tests import parity_metrics as pm
     from theatergen_amd import ops, rowchain
-    from theatergen_amd.weights_pack import rc_pack_tiles
     g = torch.Generator().manual_seed(M + inner)
     C = 320
     t = lambda *s, sc=1.0: torch.randn(*s, generator=g) * sc
@@ -193,9 +193,11 @@ def test_rc_ff_vs_fp32_reference(dtype, M, inner, proj):
     pr = x @ w1.float().T + b1.float()
     h3 = (pr[:, :inner] * F.gelu(pr[:, inner:])) @ w2.float().T + b2.float() + h.float()
     ref = h3 @ wp.float().T + bp.float() + x0.float() if proj else h3
-    s1, s2, bb2 = rowchain.pack_ff(w1, b1, gamma, beta, w2, b2)
-    got = ops.rc_ff(h, s1, s2, bb2, inner, 1e-5, wpo=rc_pack_tiles(wp, bp.float()) if proj else None, res0=x0 if proj else None)
+    s1, s2, bb2 = rowchain.pack_ff2(w1, b1, gamma, beta, w2, b2)
+    got = ops.rc_ff(h, s1, s2, bb2, inner, 1e-5, wpo=rowchain.pack_po2(wp, bp.float()) if proj else None, res0=x0 if proj else None)
     l2, mx = tols(dtype)
+    m = pm.metrics(got.float().cpu(), ref.float().cpu())
+    print(f"rc_ff M{M} inner{inner} proj{proj} {dtype}: rel_l2 {m['rel_l2']:.4e} (bound {1.5 * l2:.1e}), max_rel {m['max_rel']:.4e} (bound {1.5 * mx:.1e})")
     # three storage roundings on the way (normalised rows, hidden activations, h3 before proj_out): 1.5x the single-op tolerance
     check(got, ref, f"rc_ff M{M} inner{inner} proj{proj} {dtype}", 1.5 * l2, 1.5 * mx)
 

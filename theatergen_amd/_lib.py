@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("THEATERGEN_HIP_LIB") or os.path.join(HERE, "lib", "li
 TG_BF16, TG_F16 = 0, 1
 ABI_VERSION = 308          # TG_ABI_VERSION of include/theatergen_hip.h this binding was written against
 ACT_NONE, ACT_SILU, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2, 3
-RC_FF_TWO_WAVE = 0x10000     # TG_RC_FF_TWO_WAVE: kernel selector bit in the `dbg` word of tg_rc_ff_desc
+RC_FF_TWO_WAVE = 0x10000     # TG_RC_FF_TWO_WAVE: the stream-format tag (pack_ff2 / pack_po2) the `dbg` word of tg_rc_ff_desc must hold
 # TG_RESAMPLE_TILE_H / _TILE_W / _LDS_BYTES / _MAX_SIZE: the fused tile of tg_image_resample_u8 and its LDS budget (the host plan picks the route with them)
 RESAMPLE_TILE_H, RESAMPLE_TILE_W, RESAMPLE_LDS_BYTES, RESAMPLE_MAX_SIZE = 16, 128, 20480, 8192
 

@@ -169,7 +169,6 @@ HOT_GATES = [
     ("bt_gemm_kernel<", 132, 256),
     # row-chain kernels (round 4): straight-line register-array code — any scratch means an array fell out of the registers
     ("rc_xattn_kernel<", 0, 256),
-    ("rc_ff_kernel<", 0, 256),
     ("rc_ff2_kernel<", 0, 256),                                    # two waves per SIMD: a 257th register would halve the occupancy the kernel exists for
     ("rc_front_kernel<", 0, 216),                                  # round 4's first version spilled 108 registers (30 % of its launch)
     ("rc_linear_kernel<", 0, 256),                                 # template arguments <T, KS, NW, LN>: plain / + residual and the LayerNorm fold

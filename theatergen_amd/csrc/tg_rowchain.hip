@@ -720,20 +720,6 @@ int dispatch_rc_xattn(const tg_rc_xattn_desc* d, const RcXattnParams& p, hipStre
 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// rc_ff_kernel: norm3 + FeedForward (GEGLU) + residual, and optionally Transformer2DModel.proj_out + its residual, of a first-level block
-// in ONE launch (reference models/attention.py:226-236 `ff(norm3(x)) + x`, :328-338 GEGLU; models/transformer_2d.py:316-327 proj_out):
-//     h3 = net2( a * gelu(g) ) + b2 + h,   [a | g] = proj(LayerNorm(h)) + b1;        out = proj_out(h3) + b + res0
-// Today: layernorm (16 us) + 256 x 256 GEGLU GEMM (148 us at 65536 tokens: K = 320 is five K-tiles long) + net.2 GEMM (92 us) + proj_out
-// (27-39 us), and the [tokens, 1280] hidden tensor (168 MB) written and read back.  Here the hidden activations exist 32 channels at a
-// time, in the registers of the wave that owns the 32 tokens: per 32-channel SLICE j the wave runs 40 MFMAs of proj (value tile + gate tile
-// over the normalised rows), GEGLU on the 16 + 16 accumulator registers, and 20 MFMAs of net.2 (10 output tiles x 2 k-steps) into 160
-// accumulator registers that live for the whole kernel.  ONE wave per SIMD (the 160 + 64 accumulators, the rows and the normalised rows need
-// ~420 registers), so nothing else fills the matrix pipe while the wave does arithmetic: the stream is software-pipelined by hand —
-// iteration j issues, interleaved 2 : 1,  proj(j)'s 40 MFMAs and net.2(j - 2)'s 20 MFMAs, and between consecutive MFMAs one quarter of one
-// element of GEGLU(j - 1) (~6 VALU instructions = the issue slots one 32-cycle MFMA leaves free).
-// LDS: two 44-KiB proj slots + two 20-KiB net.2 slots (LDS-DMA, fetched one iteration ahead); the proj_out phase reuses them as three
-// 24-KiB tile stages.
-// ---------------------------------------------------------------------------------------------------------------------------------
 // rc_front_kernel: the FRONT of a first-level Transformer2DModel in one launch (SD-1.5 geometry, 320 channels):
 //     y = proj_in(GroupNorm(x)) + b;      [Q | K | V] = to_qkv(LayerNorm1(y))      (Q | K token-major [M, 640], V TRANSPOSED per batch item)
 // (models/transformer_2d.py:285-296 norm + proj_in; models/attention.py:186-204 norm1 + attn1's projections; today: GroupNorm apply pass,
@@ -1033,7 +1019,7 @@ template <int... X, class F> __device__ __forceinline__ void static_for_impl(std
 }
 template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }
 // fragment read / counted wait as asm: hipcc waits lgkmcnt(0) in front of most MFMAs of a long read-ahead stream (every such wait exposes a
-// full LDS round trip when ONE wave runs on the SIMD); the wait is tied to the fragment register so the MFMA cannot be moved above it
+// full LDS round trip: the read-ahead would hide nothing); the wait is tied to the fragment register so the MFMA cannot be moved above it
 template <int OFF, typename V8> __device__ __forceinline__ void lds_read16(V8& dst, unsigned addr) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
 }
@@ -1048,10 +1034,10 @@ template <int N, typename V8> __device__ __forceinline__ void lds_wait3(V8& f0, 
 struct RcFfParams {
   const void* h;        // [M, 320] the stream before norm3 (= the residual)
   long ldh;
-  const void* w1;       // rowchain.pack_ff (rc_ff_kernel) / pack_ff2 (rc_ff2_kernel): n_slices x 41 KiB (+ 3 KiB pad)
+  const void* w1;       // rowchain.pack_ff2: n_slices x 41 KiB (+ 3 KiB pad)
   const void* w2;       // n_slices x 20 KiB, of the same pack function
   const float* b2;      // fp32 [320]
-  const void* wpo;      // proj_out as rc_pack_tiles stream (rc_ff_kernel) / rowchain.pack_po2 stream (rc_ff2_kernel), or NULL (then `out` = h3)
+  const void* wpo;      // proj_out as rowchain.pack_po2 stream, or NULL (then `out` = h3)
   const void* res0;     // [M, 320] residual of proj_out
   long ldres;
   void* out;
@@ -1061,351 +1047,33 @@ struct RcFfParams {
   float ln_eps;
 };
 
-template <typename T, bool PROJ>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void rc_ff_kernel(RcFfParams p) {
-  typedef typename Vec<T>::v8 V8;
-  constexpr int KS = 20, NW = 4;
-  constexpr int W1B = 41 * 1024, W1SLOT = 44 * 1024, W2B = 20 * 1024;
-  constexpr int W2OFF = 2 * W1SLOT;
-  constexpr int TBW = (KS + 1) * 1024, SLOT = 24 * 1024;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, hi = lane >> 5;
-  const int lbid = rc_block_id((int)blockIdx.x, (int)gridDim.x);
-  const long tok0 = ((long)lbid * NW + wave) * 32;
-  const int qb = lane & 3;
-  long mrow[4];
-  bool mok[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const long r = tok0 + (l31 & ~3) + i;
-    mok[i] = r < p.M;
-    mrow[i] = mok[i] ? r : p.M - 1;
-  }
-  const int NS = p.n_slices;
-  const char* w1g = reinterpret_cast<const char*>(p.w1) + lane * 16 + wave * 1024;
-  const char* w2g = reinterpret_cast<const char*>(p.w2) + lane * 16 + wave * 1024;
-  auto issue_w1 = [&](int j) __attribute__((always_inline)) {      // slice j -> proj slot j & 1: 11 pieces per wave (41 KiB + 3 KiB of the next slice / the pad)
-    const char* s0 = w1g + (long)j * W1B;
-    char* dst = smem + (j & 1) * W1SLOT + wave * 1024;
-#pragma unroll
-    for (int q = 0; q < 11; ++q)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(s0 + q * NW * 1024),
-                                       (__attribute__((address_space(3))) void*)(dst + q * NW * 1024), 16, 0, 0);
-  };
-  auto issue_w2 = [&](int j) __attribute__((always_inline)) {      // slice j -> net.2 slot j & 1: 5 pieces per wave
-    const char* s0 = w2g + (long)j * W2B;
-    char* dst = smem + W2OFF + (j & 1) * W2B + wave * 1024;
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(s0 + q * NW * 1024),
-                                       (__attribute__((address_space(3))) void*)(dst + q * NW * 1024), 16, 0, 0);
-  };
-  issue_w1(0);
-
-  // rows -> B operands (H: as stored, the residual; HN: normalised, what norm3 hands to the feed-forward)
-  V8 H[KS], HN[KS];
-  {
-    const T* xp = reinterpret_cast<const T*>(p.h) + 32 * hi + 8 * qb;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) H[s] = *reinterpret_cast<const V8*>(xp + mrow[s & 3] * p.ldh + 64 * (s >> 2));
-#pragma unroll
-    for (int q = 0; q < KS / 4; ++q) quad_transpose(H[4 * q], H[4 * q + 1], H[4 * q + 2], H[4 * q + 3]);
-    float sum = 0.f;
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sum += to_f32<T>(H[s][e]);
-    sum += __shfl_xor(sum, 32, 64);
-    const float mean = sum * (1.0f / 320.0f);
-    float c2 = 0.f;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      asm volatile("" : "+v"(H[s]));
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { const float d = to_f32<T>(H[s][e]) - mean; c2 = __builtin_fmaf(d, d, c2); }
-    }
-    c2 += __shfl_xor(c2, 32, 64);
-    const float rstd = __builtin_amdgcn_rsqf(c2 * (1.0f / 320.0f) + p.ln_eps);
-    const float nm = -mean * rstd;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      asm volatile("" : "+v"(H[s]));
-      float f[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) f[e] = __builtin_fmaf(to_f32<T>(H[s][e]), rstd, nm);
-      HN[s] = pack8<T>(f);
-    }
-  }
-  // net.2's accumulators for the whole kernel: tile t = 2 c + u, register rho <-> channel 64 c + 32 hi + 16 u + rho; seeded with b2
-  f32x16 out[10];
-#pragma unroll
-  for (int t = 0; t < 10; ++t)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const f32x4 b4 = *reinterpret_cast<const f32x4*>(p.b2 + 64 * (t >> 1) + 32 * hi + 16 * (t & 1) + 4 * g);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) out[t][4 * g + e] = b4[e];
-    }
-
-  f32x16 acc_a[2], acc_g[2];
-  V8 hid[2][2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { hid[q][0][e] = from_f32<T>(0.f); hid[q][1][e] = from_f32<T>(0.f); }
-
-  // one pipeline iteration: proj(j) [F1], GEGLU(j - 1) [GG], net.2(j - 2) [F2]; PAR = j & 1 selects slots / accumulator sets
-  auto iteration = [&](int j, auto par_c, auto f1_c, auto gg_c, auto f2_c) __attribute__((always_inline)) {
-    constexpr int PAR = decltype(par_c)::value;
-    constexpr bool F1 = decltype(f1_c)::value, GG = decltype(gg_c)::value, F2 = decltype(f2_c)::value;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (j + 1 < NS) issue_w1(j + 1);
-    if (j >= 1 && j - 1 < NS) issue_w2(j - 1);
-    const char* w1b = smem + PAR * W1SLOT + lane * 16;
-    const char* w2b = smem + W2OFF + PAR * W2B + lane * 16;
-    if constexpr (F1) {
-      const float* page = reinterpret_cast<const float*>(smem + PAR * W1SLOT + 40 * 1024) + 16 * hi;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 a4 = *reinterpret_cast<const f32x4*>(page + 4 * g);
-        const f32x4 g4 = *reinterpret_cast<const f32x4*>(page + 32 + 4 * g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { acc_a[PAR][4 * g + e] = a4[e]; acc_g[PAR][4 * g + e] = g4[e]; }
-      }
-    }
-    // slot x = 3 k + {0: value tile, 1: gate tile, 2: net.2 (tile k % 10, k-step k / 10)}; the fragment of slot x is read LA slots ahead of
-    // its MFMA (asm reads, counted waits: see lds_read16)
-    constexpr int LA = 9;
-    const unsigned lbase = (unsigned)reinterpret_cast<size_t>((__attribute__((address_space(3))) char*)smem);
-    const unsigned a1 = lbase + PAR * W1SLOT + lane * 16, a2 = lbase + W2OFF + PAR * W2B + lane * 16;
-    V8 fr[60];
-    auto rd = [&](auto xc) __attribute__((always_inline)) {
-      constexpr int x = decltype(xc)::value;
-      constexpr int k = x / 3, w = x % 3;
-      if constexpr (w == 0) { if constexpr (F1) lds_read16<k * 1024>(fr[x], a1); }
-      else if constexpr (w == 1) { if constexpr (F1) lds_read16<(20 + k) * 1024>(fr[x], a1); }
-      else { if constexpr (F2) lds_read16<((k % 10) * 2 + k / 10) * 1024>(fr[x], a2); }
-    };
-    static_for<LA>([&](auto xc) __attribute__((always_inline)) { rd(xc); });
-    // GEGLU micro-step state (one element in flight).  gelu(g) = g (0.5 + 0.5 erf(g / sqrt 2)) with erf(z) = z P(z^2) on |z| <= 3 (degree-7
-    // minimax fit in z^2, |error| <= 8.1e-5, clamped beyond: erf(3) = 1 - 2.2e-5): fourteen plain VALU instructions per element and no
-    // transcendental — the quarter-rate rcp + exp2 of the Abramowitz-Stegun form cost this single-wave stream more than their issue time
-    float ge_z = 0.f, ge_t = 0.f, ge_p = 0.f;
-    float hv[8];
-    auto geglu_micro = [&](int mstep) __attribute__((always_inline)) {
-      const int e = mstep >> 2, part = mstep & 3;
-      const float a = acc_a[PAR ^ 1][e], g = acc_g[PAR ^ 1][e];
-      if (part == 0) {
-        ge_z = __builtin_amdgcn_fmed3f(g * 0.70710678118654752440f, -3.0f, 3.0f);
-        ge_t = ge_z * ge_z;
-      } else if (part == 1) {
-        float q = __builtin_fmaf(-4.0553346e-07f, ge_t, 1.7159753e-05f);
-        q = __builtin_fmaf(q, ge_t, -3.1459445e-04f);
-        q = __builtin_fmaf(q, ge_t, 3.3187051e-03f);
-        ge_p = __builtin_fmaf(q, ge_t, -2.2685785e-02f);
-      } else if (part == 2) {
-        float q = __builtin_fmaf(ge_p, ge_t, 1.0771781e-01f);
-        q = __builtin_fmaf(q, ge_t, -3.7323141e-01f);
-        q = __builtin_fmaf(q, ge_t, 1.1278958f);
-        ge_p = q * ge_z;                                     // erf(g / sqrt 2)
-      } else {
-        hv[e & 7] = a * g * __builtin_fmaf(0.5f, ge_p, 0.5f);
-        if ((e & 7) == 7) hid[PAR ^ 1][e >> 3] = pack8<T>(hv);
-      }
-    };
-    __builtin_amdgcn_sched_barrier(0);
-    static_for<60>([&](auto xc) __attribute__((always_inline)) {
-      constexpr int x = decltype(xc)::value;
-      constexpr int k = x / 3, w = x % 3;
-      constexpr bool act = (w == 2) ? F2 : F1;
-      if constexpr (F1 && F2) {
-        if constexpr (w == 0) {      // the three reads of the group LA slots ahead, in one go
-          if constexpr (x + LA < 60) rd(std::integral_constant<int, (x + LA < 60 ? x + LA : 59)>{});
-          if constexpr (x + LA + 1 < 60) rd(std::integral_constant<int, (x + LA + 1 < 60 ? x + LA + 1 : 59)>{});
-          if constexpr (x + LA + 2 < 60) rd(std::integral_constant<int, (x + LA + 2 < 60 ? x + LA + 2 : 59)>{});
-        }
-      } else {
-        if constexpr (x + LA < 60) rd(std::integral_constant<int, (x + LA < 60 ? x + LA : 59)>{});
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (act) {
-        // reads issued after this slot's: the active slots in (x, min(59, x + LA)]
-        constexpr int hi_x = x + LA < 60 ? x + LA : 59;
-        constexpr int n_f1 = ((hi_x / 3) * 2 + (hi_x % 3 >= 1 ? (hi_x % 3 == 1 ? 2 : 2) : 1)) - ((x / 3) * 2 + (x % 3 >= 1 ? 2 : 1));
-        constexpr int n_f2 = (hi_x + 1) / 3 - (x + 1) / 3;
-        constexpr int younger = (F1 ? n_f1 : 0) + (F2 ? n_f2 : 0);
-        if constexpr (F1 && F2) {
-          // steady state: one wait per slot group (value, gate, net.2 fragments of k): counted for the group's LAST fragment
-          if constexpr (w == 0) {
-            constexpr int hi3 = x + 2 + LA < 60 ? x + 2 + LA : 59;
-            lds_wait3<(hi3 - (x + 2) > 15 ? 15 : hi3 - (x + 2))>(fr[x], fr[x + 1], fr[x + 2]);
-          }
-        } else {
-          lds_wait<(younger > 15 ? 15 : younger)>(fr[x]);
-        }
-        if constexpr (w == 0) acc_a[PAR] = mfma32(fr[x], HN[k], acc_a[PAR]);
-        else if constexpr (w == 1) acc_g[PAR] = mfma32(fr[x], HN[k], acc_g[PAR]);
-        else out[k % 10] = mfma32(fr[x], hid[PAR][k / 10], out[k % 10]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (GG) {
-        // 64 micro-steps in 60 slots, ONE element in flight (the micro-step state is a handful of scalars): the last four slots take two
-        if constexpr (x < 56) geglu_micro(x);
-        else { geglu_micro(56 + 2 * (x - 56)); geglu_micro(57 + 2 * (x - 56)); }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    });
-    // anchor: the hidden pieces are consumed one iteration later, in another basic block — without a use HERE the compiler sinks the whole
-    // GEGLU arithmetic of this iteration down to that block (one lump of ~700 VALU instructions with the matrix pipe idle)
-    if constexpr (GG) asm volatile("" :: "v"(hid[PAR ^ 1][0]), "v"(hid[PAR ^ 1][1]));
-  };
-  using C0 = std::integral_constant<int, 0>;
-  using C1 = std::integral_constant<int, 1>;
-  using Tt = std::true_type;
-  using Ff = std::false_type;
-  iteration(0, C0{}, Tt{}, Ff{}, Ff{});
-  iteration(1, C1{}, Tt{}, Tt{}, Ff{});
-  for (int j = 2; j < NS; j += 2) {
-    iteration(j, C0{}, Tt{}, Tt{}, Tt{});
-    iteration(j + 1, C1{}, Tt{}, Tt{}, Tt{});
-  }
-  iteration(NS, C0{}, Ff{}, Tt{}, Tt{});
-  iteration(NS + 1, C1{}, Ff{}, Ff{}, Tt{});
-
-  // h3 = net.2 + b2 + h: the rows are read again (L2 / Infinity Cache; keeping them would cost 80 of the 512 registers for the whole
-  // pipeline); their B layout IS the accumulator layout: piece 2 t + (rho >> 3), element rho & 7
-  {
-    const T* hb = reinterpret_cast<const T*>(p.h);
-    asm volatile("" : "+s"(hb));
-    const T* xp = hb + 32 * hi + 8 * qb;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-      V8 hr[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) hr[i] = gld<V8>(xp + mrow[i] * p.ldh + 64 * c);
-      quad_transpose(hr[0], hr[1], hr[2], hr[3]);
-#pragma unroll
-      for (int uu = 0; uu < 2; ++uu)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[2 * c + uu][r] += to_f32<T>(hr[2 * uu + (r >> 3)][r & 7]);
-    }
-  }
-
-  T* outp = reinterpret_cast<T*>(p.out);
-  if constexpr (!PROJ) {
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-      V8 pc[4] = {pack8r<T>(out[2 * c], 0), pack8r<T>(out[2 * c], 8), pack8r<T>(out[2 * c + 1], 0), pack8r<T>(out[2 * c + 1], 8)};
-      quad_transpose(pc[0], pc[1], pc[2], pc[3]);
-      const long ch0 = 64 * (long)c + 32 * hi;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (mok[i]) *reinterpret_cast<V8*>(outp + mrow[i] * p.ldc + ch0 + 8 * qb) = pc[i];
-    }
-  } else {
-    // proj_out over the rounded h3 rows: 10 tile stages of 24 KiB in a ring of three (the feed-forward slots are dead behind this barrier)
-    V8 HB[KS];
-#pragma unroll
-    for (int t = 0; t < 10; ++t) { HB[2 * t] = pack8r<T>(out[t], 0); HB[2 * t + 1] = pack8r<T>(out[t], 8); }
-    const char* wpg = reinterpret_cast<const char*>(p.wpo) + lane * 16 + wave * 1024;
-    auto issue_po = [&](int st) __attribute__((always_inline)) {
-      if (st >= 10) return;
-      const char* s0 = wpg + (long)st * TBW;
-      char* dst = smem + (st % 3) * SLOT + wave * 1024;
-#pragma unroll
-      for (int q = 0; q < 6; ++q)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(s0 + q * NW * 1024),
-                                         (__attribute__((address_space(3))) void*)(dst + q * NW * 1024), 16, 0, 0);
-    };
-    __builtin_amdgcn_s_barrier();
-    issue_po(0);
-    issue_po(1);
-    V8 pend[4], r8[4];
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-#pragma unroll
-      for (int uu = 0; uu < 2; ++uu) {
-        const int st = 2 * c + uu;
-        // stage st landed when at most `younger` operations are outstanding (see rc_xattn_kernel)
-        const int younger = st == 0 ? 6 : st <= 2 ? 10 : st == 9 ? 8 : 14;
-        if (younger == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else if (younger == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        else if (younger == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        issue_po(st + 2);
-        if (uu == 0) {
-          const T* rp = reinterpret_cast<const T*>(p.res0);
-          T* op = outp;
-          asm volatile("" : "+s"(rp), "+s"(op));
-          const long ch0 = 64 * (long)c + 32 * hi;
-          if (c > 0) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-              if (mok[i]) gst<V8>(op + mrow[i] * p.ldc + (ch0 - 64) + 8 * qb, pend[i]);
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) r8[i] = gld<V8>(rp + mrow[i] * p.ldres + ch0 + 8 * qb);
-        }
-        const char* cbase = smem + (st % 3) * SLOT;
-        const char* cb = cbase + lane * 16;
-        const float* vec = reinterpret_cast<const float*>(cbase + KS * 1024) + 16 * hi;
-        constexpr int PD = 10;          // one wave per SIMD: nothing else hides the LDS round trip, and the net.2 accumulators are dead by now
-        V8 a[KS];
-#pragma unroll
-        for (int x = 0; x < PD; ++x) a[x] = *reinterpret_cast<const V8*>(cb + x * 1024);
-        f32x16 acc;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 v4 = *reinterpret_cast<const f32x4*>(vec + 4 * g);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[4 * g + e] = v4[e];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int x = 0; x < KS; ++x) {
-          if (x + PD < KS) a[x + PD] = *reinterpret_cast<const V8*>(cb + (x + PD) * 1024);
-          __builtin_amdgcn_sched_barrier(0);
-          acc = mfma32(a[x], HB[x], acc);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (uu == 0) quad_transpose(r8[0], r8[1], r8[2], r8[3]);
-        float o[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[r] = acc[r] + to_f32<T>(r8[2 * uu + (r >> 3)][r & 7]);
-        pend[2 * uu] = pack8<T>(o);
-        pend[2 * uu + 1] = pack8<T>(o + 8);
-        if (uu == 1) quad_transpose(pend[0], pend[1], pend[2], pend[3]);
-      }
-    }
-    {
-      const long ch0 = 64 * 4 + 32 * hi;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (mok[i]) *reinterpret_cast<V8*>(outp + mrow[i] * p.ldc + ch0 + 8 * qb) = pend[i];
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
-// rc_ff2_kernel: the chain of rc_ff_kernel at TWO waves per SIMD.  rc_ff_kernel's single wave per SIMD runs its interleaved stream at the SUM of its
-// MFMA and VALU issue times (profiles/r4_rowchain_findings.md) and every workgroup sits in its row-load / store phases with nothing else on the SIMD.
-// Here ONE 8-wave workgroup per CU shares one weight stream (same LDS stages, same 128 tokens per stream: the L2 -> LDS traffic does not change), and a
-// wave owns 16 tokens on v_mfma_f32_16x16x32: 80 net.2 accumulator registers (20 tiles of 16 channels), two projection slots of 16, the normalised rows
-// as 10 B pieces of 32 channels — within 256 registers.  Index maps (n = lane & 15 the token, g = lane >> 4, e = element of a 16-byte piece):
+// rc_ff2_kernel: norm3 + FeedForward (GEGLU) + residual, and optionally Transformer2DModel.proj_out + its residual, of a first-level block
+// in ONE launch (reference models/attention.py:226-236 `ff(norm3(x)) + x`, :328-338 GEGLU; models/transformer_2d.py:316-327 proj_out):
+//     h3 = net2( a * gelu(g) ) + b2 + h,   [a | g] = proj(LayerNorm(h)) + b1;        out = proj_out(h3) + b + res0
+// As separate launches: layernorm (16 us) + 256 x 256 GEGLU GEMM (148 us at 65536 tokens: K = 320 is five K-tiles long) + net.2 GEMM (92 us) +
+// proj_out (27-39 us), and the [tokens, 1280] hidden tensor (168 MB) written and read back.  Here the hidden activations exist 32 channels at a time,
+// in the registers of the wave that owns the tokens: per 32-channel SLICE j the wave runs 40 MFMAs of proj (20 value + 20 gate fragments over the
+// normalised rows), GEGLU on the accumulator registers, and 20 MFMAs of net.2 (20 output tiles of 16 channels, one k-step of 32) into accumulators that
+// live for the whole kernel.
+// TWO waves per SIMD: a single wave per SIMD (the retired one-wave kernel of 32-token waves on 32x32x16 MFMAs, profiles/rc_ff2_findings.md) runs this
+// interleaved stream at the SUM of its MFMA and VALU issue times (profiles/r4_rowchain_findings.md) and sits in its row-load / store phases with nothing
+// else on the SIMD.  ONE 8-wave workgroup per CU shares one weight stream of 128 tokens, and a wave owns 16 tokens on v_mfma_f32_16x16x32: 80 net.2
+// accumulator registers (20 tiles of 16 channels), two projection slots of 16, the normalised rows as 10 B pieces of 32 channels — within 256 registers.
+// Pipeline, software-pipelined by hand and pinned by sched_barrier: iteration j issues, interleaved 2 : 1, proj(j)'s 40 MFMAs and net.2(j - 2)'s 20
+// MFMAs (60 slots), and between consecutive MFMAs the micro-steps of GEGLU(j - 1) (8 elements x 4 parts = 32 per iteration, a few VALU instructions each).
+// LDS (128 KiB): two 44-KiB proj slots (41 KiB of a slice + 3 KiB of the next slice / the pad) + two 20-KiB net.2 slots, filled by LDS-DMA one iteration
+// ahead; the proj_out phase reuses them as a ring of three 24-KiB stages (21 KiB used).  Fragment reads are asm ds_read_b128 with counted lgkmcnt waits
+// (lds_read16 / lds_wait above): hipcc's own waits are lgkmcnt(0) in front of most MFMAs, which turns the nine-slot read-ahead into one LDS round
+// trip per MFMA.
+// Index maps (n = lane & 15 the token, g = lane >> 4, e = element of a 16-byte piece):
 //   rows as B operand, k-step s                 lane (n, g) element e = channel 32 s + 8 g + e                    (16 contiguous bytes of the row)
 //   proj tile (value / gate, u) of slice j      MFMA row r = hidden channel 32 j + 16 u + r; accumulator register i of lane group g = row 4 g + i
 //   hidden piece of slice j (net.2's B operand) element e = [u = e >> 2][i = e & 3] = hidden channel 32 j + 16 (e >> 2) + 4 g + (e & 3)
 //   net.2 / proj_out tile t = 2 s + u           MFMA row r = output channel 32 s + 8 (r >> 2) + 4 u + (r & 3): registers i of tiles 2 s, 2 s + 1 of lane
 //                                               group g ARE elements 0..3, 4..7 of the rows' B piece s (the residual, proj_out's operand, the store)
-// Streams: rowchain.pack_ff2 / pack_po2 (same byte sizes per slice / stage as pack_ff / rc_pack_tiles, fragments in the order above; fragment
-// k = 2 s + u so that consecutive MFMAs of one kind alternate between two accumulators).  The pipeline is rc_ff_kernel's: iteration j issues proj(j),
-// GEGLU(j - 1) in micro-steps between the MFMAs, net.2(j - 2); asm fragment reads with counted lgkmcnt waits.
+// Streams: rowchain.pack_ff2 (41 KiB + 20 KiB per slice) / pack_po2 (21 KiB per stage), fragments in the order above; fragment k = 2 s + u so that
+// consecutive MFMAs of one kind alternate between two accumulators.
 template <typename T, bool PROJ>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void rc_ff2_kernel(RcFfParams p) {
   typedef typename Vec<T>::v8 V8;
@@ -1524,8 +1192,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       lds_read16<192>(acc_g[PAR][1], ap);
     }
     static_for<LA>([&](auto xc) __attribute__((always_inline)) { rd(xc); });
-    // GEGLU micro-step state (one element in flight), rc_ff_kernel's arithmetic: gelu(g) = g (0.5 + 0.5 erf(g / sqrt 2)), erf(z) = z P(z^2) on |z| <= 3.
-    // 8 elements x 4 parts = 32 micro-steps spread over the 60 slots
+    // GEGLU micro-step state (one element in flight).  gelu(g) = g (0.5 + 0.5 erf(g / sqrt 2)) with erf(z) = z P(z^2) on |z| <= 3 (degree-7 minimax fit
+    // in z^2, |error| <= 8.1e-5, clamped beyond: erf(3) = 1 - 2.2e-5): fourteen plain VALU instructions per element and no transcendental (the quarter-rate
+    // rcp + exp2 of the Abramowitz-Stegun form cost the stream more than their issue time).  8 elements x 4 parts = 32 micro-steps spread over the 60 slots
     float ge_z = 0.f, ge_t = 0.f, ge_p = 0.f;
     float hv[8];
     auto geglu_micro = [&](int mstep) __attribute__((always_inline)) {
@@ -1593,7 +1262,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
       }
     });
-    // anchor (see rc_ff_kernel): without a use HERE the compiler sinks this iteration's GEGLU arithmetic into the next iteration's block
+    // anchor: the hidden piece is consumed one iteration later, in another basic block — without a use HERE the compiler sinks this iteration's GEGLU
+    // arithmetic down to that block (one lump of VALU instructions with the matrix pipe idle)
     if constexpr (GG) asm volatile("" :: "v"(hid[PAR ^ 1]));
   };
   using C0 = std::integral_constant<int, 0>;
@@ -1706,27 +1376,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-// one instantiation, hence one `static` attribute call, per KERNEL (the four kernels share the type void (*)(RcFfParams): a helper taking the kernel as
-// a function argument would set the dynamic-LDS attribute for the first one launched only)
-template <void (*K)(RcFfParams)>
-void launch_rc_ff_kernel(long grid, int threads, size_t lds, hipStream_t st, const RcFfParams& p) {
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)attr;
-  hipLaunchKernelGGL(K, dim3((unsigned)grid), dim3(threads), lds, st, p);
-}
-
-template <typename T>
+// one 8-wave workgroup per 128 tokens; one instantiation, hence one `static` attribute call, per kernel instance
+template <typename T, bool PROJ>
 int launch_rc_ff(const tg_rc_ff_desc* d, const RcFfParams& p, hipStream_t st) {
   const size_t lds = 2 * 44 * 1024 + 2 * 20 * 1024;
-  const long grid = (d->M + 127) / 128;
-  const bool two = (d->dbg & TG_RC_FF_TWO_WAVE) != 0;      // streams of pack_ff2 / pack_po2
-  if (d->wpo != nullptr) {
-    if (two) launch_rc_ff_kernel<rc_ff2_kernel<T, true>>(grid, 512, lds, st, p);
-    else launch_rc_ff_kernel<rc_ff_kernel<T, true>>(grid, 256, lds, st, p);
-  } else {
-    if (two) launch_rc_ff_kernel<rc_ff2_kernel<T, false>>(grid, 512, lds, st, p);
-    else launch_rc_ff_kernel<rc_ff_kernel<T, false>>(grid, 256, lds, st, p);
-  }
+  auto k = rc_ff2_kernel<T, PROJ>;
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)attr;
+  hipLaunchKernelGGL(k, dim3((unsigned)((d->M + 127) / 128)), dim3(512), lds, st, p);
   TG_LAUNCH_CHECK();
   return TG_OK;
 }
@@ -1834,13 +1491,15 @@ extern "C" int tg_rc_ff(const tg_rc_ff_desc* d, void* stream) {
   TG_CHECK(d->inner >= 64 && d->inner % 64 == 0, TG_ERR_ARG, "tg_rc_ff: inner = %d must be a multiple of 64", d->inner);
   TG_CHECK(d->ldh >= 320 && d->ldh % 8 == 0 && d->ldc >= 320 && d->ldc % 8 == 0, TG_ERR_ARG, "tg_rc_ff: row pitches");
   TG_CHECK(!d->wpo || (d->res0 && d->ldres >= 320 && d->ldres % 8 == 0), TG_ERR_ARG, "tg_rc_ff: proj_out needs its residual");
-  TG_CHECK((d->dbg & ~TG_RC_FF_TWO_WAVE) == 0, TG_ERR_ARG, "tg_rc_ff: dbg = %d (TG_RC_FF_TWO_WAVE is its only bit, the rest is reserved)", d->dbg);
+  TG_CHECK(d->dbg != 0, TG_ERR_ARG,
+           "tg_rc_ff: dbg = 0: the one-wave kernel and its stream format were retired; pack with rowchain.pack_ff2 / pack_po2 and set TG_RC_FF_TWO_WAVE");
+  TG_CHECK(d->dbg == TG_RC_FF_TWO_WAVE, TG_ERR_ARG, "tg_rc_ff: dbg = %d (must be TG_RC_FF_TWO_WAVE, the stream-format tag; the rest is reserved)", d->dbg);
   RcFfParams p;
   p.h = d->h; p.ldh = d->ldh; p.w1 = d->w1; p.w2 = d->w2; p.b2 = d->b2; p.wpo = d->wpo; p.res0 = d->res0; p.ldres = d->ldres;
   p.out = d->out; p.ldc = d->ldc; p.M = d->M; p.n_slices = d->inner / 32; p.ln_eps = d->ln_eps;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->dtype == TG_BF16) return launch_rc_ff<bf16_t>(d, p, st);
-  return launch_rc_ff<f16_t>(d, p, st);
+  if (d->dtype == TG_BF16) return d->wpo ? launch_rc_ff<bf16_t, true>(d, p, st) : launch_rc_ff<bf16_t, false>(d, p, st);
+  return d->wpo ? launch_rc_ff<f16_t, true>(d, p, st) : launch_rc_ff<f16_t, false>(d, p, st);
 }
 
 extern "C" int tg_rc_front(const tg_rc_front_desc* d, void* stream) {

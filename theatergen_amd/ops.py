@@ -345,9 +345,9 @@ def rc_xattn(h, wq, kv, wo, rows_per_batch, ln_eps, ip_tokens, ip_scale=None, ou
     return out
 
 
-def rc_ff(h, w1, w2, b2, inner, ln_eps, wpo=None, res0=None, out=None, two_wave=False, _reserved=0):
-    """norm3 + GEGLU feed-forward + residual (+ proj_out + its residual) in one launch; see tg_rc_ff.  ``two_wave``: the streams are
-    ``rowchain.pack_ff2`` / ``pack_po2`` and the launch is ``rc_ff2_kernel`` (two waves per SIMD).  ``_reserved``: as in ``rc_linear``"""
+def rc_ff(h, w1, w2, b2, inner, ln_eps, wpo=None, res0=None, out=None, _reserved=0):
+    """norm3 + GEGLU feed-forward + residual (+ proj_out + its residual) in one launch; see tg_rc_ff.  The streams are ``rowchain.pack_ff2`` /
+    ``pack_po2`` and the launch is ``rc_ff2_kernel`` (two waves per SIMD).  ``_reserved``: as in ``rc_linear``"""
     from ._lib import RcFfDesc
     _need_cuda(h)
     M, Cc = h.shape
@@ -360,9 +360,9 @@ def rc_ff(h, w1, w2, b2, inner, ln_eps, wpo=None, res0=None, out=None, two_wave=
     d.w1, d.w2, d.b2, d.wpo = _ptr(w1), _ptr(w2), _ptr(b2), _ptr(wpo)
     d.res0, d.ldres = (_ptr(res0), int(res0.stride(0))) if res0 is not None else (None, 0)
     d.out, d.ldc = _ptr(out), int(out.stride(0))
-    d.M, d.inner, d.ln_eps, d.dbg = int(M), int(inner), float(ln_eps), int(_reserved) | (_lib.RC_FF_TWO_WAVE if two_wave else 0)
+    d.M, d.inner, d.ln_eps, d.dbg = int(M), int(inner), float(ln_eps), int(_reserved) | _lib.RC_FF_TWO_WAVE
     fl = 2.0 * M * 320 * (3 * int(inner)) + (2.0 * M * 320 * 320 if wpo is not None else 0.0)
-    _profiled(lambda: _lib.check(_lib.lib().tg_rc_ff(C.byref(d), _stream())), ("rc_ff2_kernel<320>" if two_wave else "rc_ff_kernel<320>") + ("+proj_out" if wpo is not None else ""),
+    _profiled(lambda: _lib.check(_lib.lib().tg_rc_ff(C.byref(d), _stream())), "rc_ff2_kernel<320>" + ("+proj_out" if wpo is not None else ""),
               M, 320, 3 * int(inner), fl, True,
               alg_bytes=2.0 * ((4 if wpo is not None else 3) * M * 320 + 3 * 320 * int(inner) + (320 * 320 if wpo is not None else 0)))
     return out

@@ -14,10 +14,10 @@ from .weights_pack import rc_pack, rc_pack_tiles
 # TG_RC: 0 = the row-chain kernels are never selected (old-path A/B), 1 = default.  TG_RC_MIN_ROWS: below this many token rows the
 # LDS-tiled GEMMs / the three-launch cross-attention stay (a row-chain workgroup is a long serial chain: it needs a full chip of them)
 ENABLED = os.environ.get("TG_RC", "1") != "0"
-# dev A/B bits: 0 tg_rc_linear swaps (K = 320), 1 tg_rc_xattn, 2 tg_rc_ff, 3 tg_rc_front, 5 tg_rc_ff on its two-waves-per-SIMD kernel
-# (rc_ff2_kernel, streams of pack_ff2 / pack_po2; without the bit: rc_ff_kernel, one wave per SIMD).  (Bit 4 was round 4's K = 640 kernel.)
-MODE = int(os.environ.get("TG_RC_MODE", "47"))
-FF_TWO_WAVE = ops._lib.RC_FF_TWO_WAVE          # TG_RC_FF_TWO_WAVE of include/theatergen_hip.h (``dbg`` word of tg_rc_ff_desc)
+# dev A/B bits: 0 tg_rc_linear swaps (K = 320), 1 tg_rc_xattn, 2 tg_rc_ff, 3 tg_rc_front.  (Bit 4 was round 4's K = 640 kernel, bit 5 chose between
+# tg_rc_ff's two kernels until the one-wave kernel was retired: higher bits are ignored, 47 in an old job file means 15.)
+MODE = int(os.environ.get("TG_RC_MODE", "15"))
+FF_TWO_WAVE = ops._lib.RC_FF_TWO_WAVE          # TG_RC_FF_TWO_WAVE of include/theatergen_hip.h: the stream-format tag in the ``dbg`` word of tg_rc_ff_desc
 MIN_ROWS = int(os.environ.get("TG_RC_MIN_ROWS", "8192"))
 # rc_linear / rc_front / rc_ff are one long serial chain per workgroup (a lone rc_ff workgroup needs ~95 us): below one full round of 128-token
 # workgroups (256 CUs x 128 rows) the LDS-tiled launches are as fast or faster (8192 rows: rc_ff 95 us vs 64 us, rc_front 51 + 16 vs 59 us)
@@ -127,59 +127,7 @@ def xattn_eligible(attn, C, B, N, L, T, dtype):
 
 
 # ---- tg_rc_ff: norm3 + FeedForward (GEGLU) + residual (+ proj_out + residual) of a first-level block in one launch --------------------
-def _ff_row_of():
-    """MFMA row r of an FF1 tile -> offset of its hidden channel inside the 32-channel slice: accumulator register rho of lane half hi
-    (row = (rho & 3) + 8 (rho >> 2) + 4 hi) holds hidden channel 16 hi + rho"""
-    r = torch.arange(32)
-    rho = (r & 3) + 4 * (r >> 3)
-    hi = (r >> 2) & 1
-    return 16 * hi + rho
-
-
-def pack_ff(w1, b1, gamma, beta, w2, b2):
-    """``GEGLU.proj`` [2 * inner, 320] (+ bias) behind LayerNorm(gamma, beta) and ``net.2`` [320, inner] (+ bias) -> the streams of
-    ``tg_rc_ff`` (reference models/attention.py:226-236, 328-338; inner = 1280):
-      * w1 stream: per 32-channel hidden slice j: 20 fragment blocks of the VALUE rows, 20 of the GATE rows (K order = the row layout of
-        ``rc_pack``), then one 1-KiB page: fp32 bias_a[32], bias_g[32] in accumulator order, W * gamma folded, bias + W beta folded;
-        the kernel normalises the rows itself ((x - mean) * rstd rounded to the storage dtype: what ``norm3`` hands to ``ff``), 3 KiB pad;
-      * w2 stream: per slice j: 10 output tiles x 2 k-steps of ``net.2`` columns [32 j, 32 j + 32) (20 KiB);
-      * b2: fp32 [320]."""
-    from .weights_pack import _rc_maps
-    inner = w2.shape[1]
-    assert w1.shape == (2 * inner, C) and w2.shape == (C, inner) and inner % 32 == 0
-    dev, dt = w1.device, w1.dtype
-    g32, be32 = gamma.detach().float(), beta.detach().float()
-    w1f = w1.detach().float()
-    w1g = (w1f * g32[None, :]).to(dt)                                   # rounded once, like pack_ln_linear
-    v1 = w1f @ be32 + (b1.detach().float() if b1 is not None else 0.0)   # [2 * inner]
-    pi, kap = _rc_maps(C)
-    kap = kap.to(dev)                                                   # [s, hi, j] -> input channel
-    rowoff = _ff_row_of().to(dev)                                       # [r] -> hidden offset in the slice
-    ns = inner // 32
-    hid = 32 * torch.arange(ns, device=dev)[:, None] + rowoff[None, :]  # [slice, r]
-    rows_a, rows_g = hid, inner + hid
-    # frag[slice, which(a / g), s, hi, r, j] = w1g[row(slice, which, r), kap[s, hi, j]]
-    rows = torch.stack([rows_a, rows_g], dim=1)                          # [slice, 2, r]
-    frag = w1g[rows[:, :, None, None, :, None], kap[None, None, :, :, None, :]].contiguous()
-    fb = frag.reshape(ns, -1).view(torch.uint8)                          # [slice, 40 KiB]
-    page = torch.zeros(ns, 256, dtype=torch.float32, device=dev)
-    acc_ch = (16 * torch.arange(2, device=dev)[:, None] + torch.arange(16, device=dev)[None, :]).reshape(-1)   # index 16 hi + rho -> hidden offset
-    page[:, :32] = v1[(32 * torch.arange(ns, device=dev)[:, None] + acc_ch[None, :])]
-    page[:, 32:64] = v1[inner + (32 * torch.arange(ns, device=dev)[:, None] + acc_ch[None, :])]
-    s1 = torch.cat([fb, page.view(torch.uint8)], dim=1).reshape(-1)
-    s1 = torch.cat([s1, torch.zeros(3 * 1024, dtype=torch.uint8, device=dev)])
-    # w2: block (slice, t = 2 c + u, kk): lane (hi, r), element j = w2[64 c + pi(u, r), 32 slice + 16 hi + 8 kk + j]
-    out_rows = (64 * torch.arange(C // 64)[:, None, None] + pi[None]).reshape(-1, 32).to(dev)      # [t, r]
-    kcol = (32 * torch.arange(ns, device=dev)[:, None, None, None] + 16 * torch.arange(2, device=dev)[None, None, :, None]
-            + 8 * torch.arange(2, device=dev)[None, :, None, None] + torch.arange(8, device=dev)[None, None, None, :])   # [slice, kk, hi, j]
-    w2d = w2.detach()
-    f2 = w2d[out_rows[None, :, None, None, :, None], kcol[:, None, :, :, None, :]].contiguous()    # [slice, t, kk, hi, r, j]
-    s2 = f2.reshape(-1).view(torch.uint8)
-    bb2 = (b2.detach().float() if b2 is not None else torch.zeros(C, device=dev)).contiguous()
-    return s1.contiguous(), s2.contiguous(), bb2
-
-
-# ---- tg_rc_ff on rc_ff2_kernel: 16 tokens per wave on 16x16x32 MFMAs (A fragment: lane (r = lane & 15, g = lane >> 4) holds row r, k = 8 g + e) -------
+# rc_ff2_kernel: 16 tokens per wave on 16x16x32 MFMAs (A fragment: lane (r = lane & 15, g = lane >> 4) holds row r, k = 8 g + e)
 def _ff2_out_row():
     """MFMA row r of output tile t = 2 s + u -> offset of its channel inside the 32-channel group s, per u: accumulator register i of lane group g
     (row 4 g + i) holds channel 32 s + 8 g + 4 u + i — elements 4 u + i of the rows' 16-byte B piece s"""
@@ -188,7 +136,10 @@ def _ff2_out_row():
 
 
 def pack_ff2(w1, b1, gamma, beta, w2, b2):
-    """As ``pack_ff`` for ``rc_ff2_kernel`` (same folds, same sizes: 41 KiB + 20 KiB per 32-channel hidden slice j, 3 KiB pad):
+    """``GEGLU.proj`` [2 * inner, 320] (+ bias) behind LayerNorm(gamma, beta) and ``net.2`` [320, inner] (+ bias) -> the streams of ``tg_rc_ff``
+    (``rc_ff2_kernel``; reference models/attention.py:226-236, 328-338; inner = 1280): 41 KiB + 20 KiB per 32-channel hidden slice j, 3 KiB pad.
+    W' = W * gamma rounded once to the storage dtype, bias + W beta folded into the page; the kernel normalises the rows itself ((x - mean) * rstd
+    rounded to the storage dtype: what ``norm3`` hands to ``ff``):
       * w1 stream: 20 VALUE fragments k = 2 s + u, 20 GATE fragments, lane (r, g), element e = W'[32 j + 16 u + r (+ inner), 32 s + 8 g + e]; then the
         1-KiB page: fp32 bias_a[32], bias_g[32] in hidden-channel order;
       * w2 stream: 20 fragments, tile t = 2 s + u: lane (r, g), element e = net.2[32 s + 8 (r >> 2) + 4 u + (r & 3), 32 j + 16 (e >> 2) + 4 g + (e & 3)]

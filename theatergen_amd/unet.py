@@ -236,16 +236,13 @@ class FeedForward(nn.Module):
                 or x2d.stride(0) != K or proj.weight.shape[0] != 2 * inner):
             return None
         ts = [proj.weight, proj.bias, norm.weight, norm.bias, lin2.weight] + ([lin2.bias] if lin2.bias is not None else [])
-        two = bool(rowchain.MODE & 32)        # rc_ff2_kernel (two waves per SIMD): its own fragment order, cached beside the one-wave streams
-        pack = rowchain.pack_ff2 if two else rowchain.pack_ff
-        s1, s2, b2 = self._p.get("rc_ff2" if two else "rc_ff", ts, lambda: pack(proj.weight, proj.bias, norm.weight, norm.bias, lin2.weight, lin2.bias))
+        s1, s2, b2 = self._p.get("rc_ff2", ts, lambda: rowchain.pack_ff2(proj.weight, proj.bias, norm.weight, norm.bias, lin2.weight, lin2.bias))
         wpo = res0 = None
         if tail is not None:
             w_out, b_out, res0 = tail
-            pack_po = rowchain.pack_po2 if two else rc_pack_tiles
-            wpo = self._p.get("rc_po2" if two else "rc_po", [w_out] + ([b_out] if b_out is not None else []),
-                              lambda: pack_po(w_out.detach(), b_out.detach().float() if b_out is not None else None))
-        return ops.rc_ff(x2d, s1, s2, b2, inner, norm.eps, wpo=wpo, res0=res0, two_wave=two)
+            wpo = self._p.get("rc_po2", [w_out] + ([b_out] if b_out is not None else []),
+                              lambda: rowchain.pack_po2(w_out.detach(), b_out.detach().float() if b_out is not None else None))
+        return ops.rc_ff(x2d, s1, s2, b2, inner, norm.eps, wpo=wpo, res0=res0)
 
     def _hidden(self, M, inner, like):
         """the [M, inner] hidden tensor.  Round 5: when its row pitch would be a multiple of 1 KiB (inner = 2560 / 5120: the 32 x 32 / 16 x 16 levels) the rows are

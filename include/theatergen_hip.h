@@ -1112,6 +1112,41 @@ int tg_dino_box_update(int32_t dtype, int64_t rows, int32_t rows_per_batch, int3
                        const float* prior, int32_t prior_is_box, const float* valid_ratios, int32_t n_levels, float* ref, float* ref_levels,
                        void* pos_in, int64_t pos_ld, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The lineart annotator (controlnet_aux lineart Generator(3, 1, n_residual_blocks = 3): stage 2's ControlNet control image; csrc/tg_lineart.hip).
+ * Additive to ABI 308: new symbols only.  Activations are token-major NHWC [batch][h * w][c] in the storage dtype; the 3x3 convs between these layers are
+ * tg_gemm mode 1 (stride 1 / 2; the stride-2 transposed convs as a zero-padded 3x3 conv with 4 N output channels, one block of N per output parity
+ * class, or tg_conv_up2 where it takes the layer).
+ *
+ * tg_lineart_instnorm: nn.InstanceNorm2d defaults (no affine, biased variance, statistics per (image, channel) over the h * w pixels, fp32), then
+ *   optionally ReLU, then optionally + res; one rounding to the storage dtype.  Three launches: per-slab (count, mean, M2) of shifted sums, one
+ *   sequential Chan merge of the slabs per (image, channel), apply.  No atomics and no arrival counters: the summation order is a function of (h, w, c)
+ *   alone, so a run is bit-reproducible and an image's result does not depend on the batch it is in.
+ *   x_layout / res_layout  0: dense [batch][h * w][c].
+ *                          1: the INTERIOR of a reflect-bordered image [batch][(h + 2) * (w + 2)][c] (what out_border = 1 writes, and what a pad-1 3x3
+ *                             conv run over such an image returns).
+ *                          2 (x only): [batch][(h / 2) * (w / 2)][4 c], pixel (2 i + py, 2 j + px) = channels [(2 py + px) c, (2 py + px + 1) c) of
+ *                             low-resolution pixel (i, j): the parity-class output of a stride-2 transposed conv before its pixel shuffle; h, w even.
+ *   out_border             0: out is dense [batch][h * w][c].  1: out is [batch][(h + 2) * (w + 2)][c] with the one-pixel border filled by reflection
+ *                             (row -1 = row 1, row h = row h - 2, columns alike): nn.ReflectionPad2d(1) as address arithmetic; h, w >= 2.
+ *   scratch                tg_lineart_instnorm_scratch_bytes(batch, h, w, c) bytes of device memory (-1: unsupported shape), 16-byte aligned.
+ *   c in {64, 128, 256}; x, res, out 16-byte aligned; out must not alias x or res.  TG_ERR_ARG otherwise.
+ *
+ * tg_lineart_conv7_in: ReflectionPad2d(3) + Conv2d(3, 64, 7) + bias.  x is the NCHW image [batch][3][h][w] in the storage dtype (tg_image_from_u8,
+ *   range_mode 0), wt fp32 [147][64] with row (ci * 7 + ky) * 7 + kx, bias fp32 [64], out [batch][h * w][64].  fp32 FMAs on the stored operands, one
+ *   rounding.  A 22 x 22 x 3 reflected halo tile per 16 x 16 output pixels in LDS.  h, w >= 4.
+ *
+ * tg_lineart_conv7_out: ReflectionPad2d(3) + Conv2d(64, 1, 7) + bias + sigmoid, then the annotator's byte step: out_u8[b][y][x][0..2] =
+ *   255 - min(max(trunc(255 s), 0), 255), s = 1 / (1 + exp(-t)) in fp32 (truncation, as ndarray.astype(uint8) does).  x [batch][h * w][64], wt fp32
+ *   [49][64] with row ky * 7 + kx, out_u8 uint8 RGB [batch][h][w][3] (the map replicated), out_sigmoid optional fp32 [batch][h][w] = s.  A 22 x 14
+ *   reflected halo tile per 16 x 8 output pixels in LDS in the storage dtype.  h, w >= 4; x 16-byte aligned. */
+int64_t tg_lineart_instnorm_scratch_bytes(int32_t batch, int32_t h, int32_t w, int32_t c);
+int tg_lineart_instnorm(int32_t dtype, const void* x, int32_t x_layout, int32_t batch, int32_t h, int32_t w, int32_t c, float eps, int32_t relu,
+                        const void* res, int32_t res_layout, void* out, int32_t out_border, void* scratch, void* stream);
+int tg_lineart_conv7_in(int32_t dtype, const void* x, int32_t batch, int32_t h, int32_t w, const void* wt, const void* bias, void* out, void* stream);
+int tg_lineart_conv7_out(int32_t dtype, const void* x, int32_t batch, int32_t h, int32_t w, const void* wt, float bias, void* out_u8,
+                         void* out_sigmoid, void* stream);
+
 /* debugging aid: raw 32x32x16 MFMA on caller-provided fragments (64 lanes x 8 elements each) */
 int tg_debug_mfma32(int32_t dtype, const void* a_frags, const void* b_frags, float* d_out, void* stream);
 

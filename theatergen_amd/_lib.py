@@ -222,6 +222,10 @@ SIGNATURES = {
     "tg_xq_kv_pack": (i32, [i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp]),
     "tg_dino_contrastive": (i32, [i32, i32, i32, i32, i32, i32, vp, i64, i64, vp, i64, i64, vp, vp, vp, vp]),
     "tg_dino_box_update": (i32, [i32, i64, i32, i32, vp, i64, vp, vp, vp, i32, vp, i32, vp, vp, vp, i64, vp]),
+    "tg_lineart_instnorm_scratch_bytes": (i64, [i32, i32, i32, i32]),
+    "tg_lineart_instnorm": (i32, [i32, vp, i32, i32, i32, i32, i32, f32, i32, vp, i32, vp, i32, vp, vp]),
+    "tg_lineart_conv7_in": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "tg_lineart_conv7_out": (i32, [i32, vp, i32, i32, i32, vp, f32, vp, vp, vp]),
     "tg_debug_mfma32": (i32, [i32, vp, vp, vp, vp]),
 }
 

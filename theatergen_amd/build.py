@@ -200,6 +200,15 @@ HOT_GATES = [
     ("image_resample_fused_kernel<", 0, 64),
     ("image_resample_h_kernel", 0, 64),
     ("image_resample_v_kernel<", 0, 64),
+    # the lineart annotator's own layers (tg_lineart.hip; <T>).  The 7x7 3 -> 64 conv holds 4 pixels x 16 channels of fp32 accumulators and a 10-value input
+    # row with compile-time indices (scratch = one of them was indexed at run time); the 64 -> 1 conv four partial sums and the 16-byte units of a tap row in flight (130 VGPRs:
+    # three waves per SIMD, which is also what its 44 KB halo tile allows); the InstanceNorm passes 8 channels per thread (statistics: shift, sum and sum of
+    # squares each).  Allowances = what the build reports
+    ("lineart_conv7_in_kernel<", 0, 80),
+    ("lineart_conv7_out_kernel<", 0, 130),
+    ("lineart_in_stats_kernel<", 0, 46),
+    ("lineart_in_finalize_kernel", 0, 21),
+    ("lineart_in_apply_kernel<", 0, 38),
 ]
 
 

@@ -1367,7 +1367,68 @@ def image_to_u8(images, out=None):
     return out
 
 
-resample_launches = {"fused": 0, "two_launch": 0}            # calls of image_resample_u8 by route (tests and timing scripts read it)
+LINEART_DENSE, LINEART_BORDER, LINEART_PARITY = 0, 1, 2      # x_layout / res_layout of tg_lineart_instnorm
+
+
+def lineart_instnorm(x, batch, h, w, c, *, layout=LINEART_DENSE, relu=False, res=None, res_layout=LINEART_DENSE, border=False, eps=1e-5, out=None):
+    """``nn.InstanceNorm2d(c)`` (defaults) [+ ReLU] [+ res] of the h x w image held in ``x`` (see tg_lineart_instnorm for the three input layouts) ->
+    token-major [batch * h * w, c], or with ``border`` the reflect-1 padded image [batch * (h + 2) * (w + 2), c] a pad-1 ``conv3x3`` then takes."""
+    _need_cuda(x)
+    L = _lib.lib()
+    need = L.tg_lineart_instnorm_scratch_bytes(int(batch), int(h), int(w), int(c))
+    if need < 0:
+        raise RuntimeError(f"theatergen_amd: lineart_instnorm takes c in (64, 128, 256), got batch {batch}, {h} x {w} x {c}")
+    rows_in = {LINEART_DENSE: h * w, LINEART_BORDER: (h + 2) * (w + 2), LINEART_PARITY: h * w}
+    if x.numel() != batch * rows_in[layout] * c or not x.is_contiguous():
+        raise ValueError(f"lineart_instnorm: x must be dense with {batch * rows_in[layout] * c} elements for layout {layout}, got {tuple(x.shape)}")
+    if res is not None and (res.numel() != batch * rows_in[res_layout] * c or not res.is_contiguous() or res.dtype != x.dtype):
+        raise ValueError(f"lineart_instnorm: res must be dense {x.dtype} with {batch * rows_in[res_layout] * c} elements, got {tuple(res.shape)}")
+    rows = batch * ((h + 2) * (w + 2) if border else h * w)
+    if out is None:
+        out = torch.empty((rows, c), dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (rows, c) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError(f"lineart_instnorm: out must be a contiguous {x.dtype} tensor of shape {(rows, c)}")
+    scratch = workspace(need, x.device)
+    _lib.check(L.tg_lineart_instnorm(_dt(x), _ptr(x), int(layout), int(batch), int(h), int(w), int(c), float(eps), 1 if relu else 0, _ptr(res),
+                                     int(res_layout), _ptr(out), 1 if border else 0, _ptr(scratch), _stream()))
+    return out
+
+
+def lineart_conv7_in(image, w_packed, bias, out=None):
+    """``ReflectionPad2d(3)`` + ``Conv2d(3, 64, 7)`` of the NCHW image [B, 3, H, W] (bf16 / fp16) -> token-major [B * H * W, 64]; ``w_packed`` =
+    ``weights_pack.pack_conv7x7_fp32`` (fp32 [147, 64]), ``bias`` fp32 [64]."""
+    _need_cuda(image)
+    if image.dim() != 4 or image.shape[1] != 3:
+        raise ValueError(f"lineart_conv7_in: [B, 3, H, W] expected, got {tuple(image.shape)}")
+    if w_packed.dtype != torch.float32 or tuple(w_packed.shape) != (147, 64) or bias.dtype != torch.float32 or bias.numel() != 64:
+        raise ValueError("lineart_conv7_in: w_packed must be fp32 [147, 64] and bias fp32 [64]")
+    B, _, H, W = image.shape
+    image = image.contiguous()
+    if out is None:
+        out = torch.empty((B * H * W, 64), dtype=image.dtype, device=image.device)
+    _lib.check(_lib.lib().tg_lineart_conv7_in(_dt(image), _ptr(image), B, H, W, _ptr(w_packed.contiguous()), _ptr(bias.contiguous()), _ptr(out), _stream()))
+    return out
+
+
+def lineart_conv7_out(x, batch, h, w, w_packed, bias, want_sigmoid=False, out=None):
+    """``ReflectionPad2d(3)`` + ``Conv2d(64, 1, 7)`` + sigmoid + the annotator's byte step over token-major x [batch * h * w, 64] -> uint8 RGB
+    [batch, h, w, 3] holding ``255 - trunc(255 s)`` three times (and, with ``want_sigmoid``, s as fp32 [batch, h, w]).  ``w_packed`` =
+    ``weights_pack.pack_conv7x7_to1_fp32`` (fp32 [49, 64]); ``bias`` a Python float."""
+    _need_cuda(x)
+    if x.numel() != batch * h * w * 64 or not x.is_contiguous():
+        raise ValueError(f"lineart_conv7_out: x must be dense [{batch * h * w}, 64], got {tuple(x.shape)}")
+    if w_packed.dtype != torch.float32 or tuple(w_packed.shape) != (49, 64) or not w_packed.is_contiguous():
+        raise ValueError("lineart_conv7_out: w_packed must be contiguous fp32 [49, 64]")
+    if out is None:
+        out = torch.empty((batch, h, w, 3), dtype=torch.uint8, device=x.device)
+    elif tuple(out.shape) != (batch, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError(f"lineart_conv7_out: out must be a contiguous uint8 tensor of shape {(batch, h, w, 3)}")
+    sig = torch.empty((batch, h, w), dtype=torch.float32, device=x.device) if want_sigmoid else None
+    _lib.check(_lib.lib().tg_lineart_conv7_out(_dt(x), _ptr(x), int(batch), int(h), int(w), _ptr(w_packed), float(bias), _ptr(out), _ptr(sig), _stream()))
+    return (out, sig) if want_sigmoid else out
+
+
+resample_launches = {"fused": 0, "two_launch": 0}           # calls of image_resample_u8 by route (tests and timing scripts read it)
 
 
 def image_resample_u8(images, plan_v, plan_h, lut, dtype, window=None, pad=None, out=None, u8_out=None, route=None):

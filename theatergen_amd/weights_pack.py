@@ -4,6 +4,8 @@ the HIP kernels read.  Token-major activations want K-contiguous weights:
   Conv1x1 [N, C, 1, 1]      -> [N, C]
   Conv3x3 [N, C, 3, 3]      -> [N, 9*C] tap-major (ky, kx, c)  (implicit-GEMM K order of tg_gemm mode 1)
   Upsample2D's conv         -> [4, N, 4*C] parity-class-major, folded taps (ty, tx, c)  (tg_conv_up2)
+  ConvTranspose2d 3x3 s2    -> the same [4, N, 4*C] with zero weights on the unused taps, or [4*N, 9*C] for a pad-1 conv on the low-resolution grid
+  Conv7x7 (lineart)         -> fp32 [C*49, N] / [49, C]
 """
 import torch
 
@@ -31,6 +33,61 @@ def pack_conv3x3_up2(w: torch.Tensor) -> torch.Tensor:
                 for tx in range(2):
                     out[2 * py + px, :, ty, tx] = sum(acc[:, :, ky, kx] for ky in _UP2_ROWS[py][ty] for kx in _UP2_ROWS[px][tx])
     return out.reshape(4, n, 4 * c).to(w.dtype).contiguous()
+
+
+_CONVT_TAPS = ((None, 1), (2, 0))                 # [parity][2x2 tap] -> tap of the transposed conv's 3x3 kernel (None: the tap is not used)
+
+
+def pack_convT3x3_s2_up2(w: torch.Tensor) -> torch.Tensor:
+    """``ConvTranspose2d(C, N, 3, stride=2, padding=1, output_padding=1)`` weight [C, N, 3, 3] -> tg_conv_up2's layout [4, N, 4*C] in w's dtype.
+    Output row 2i takes tap ky = 1 at input row i; row 2i + 1 takes ky = 2 at row i and ky = 0 at row i + 1 (columns alike).  In tg_conv_up2's 2x2-tap
+    classes, (ty, tx) of output pixel (2i + py, 2j + px) reads input pixel (i + py + ty - 1, j + px + tx - 1): the taps a class does not use are zero
+    weights, and the kernel's zero padding past the last row / column is ``output_padding=1``'s.  A permutation with zeros: nothing is summed or rounded."""
+    c, n, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    out = torch.zeros(4, n, 2, 2, c, dtype=w.dtype, device=w.device)
+    wd = w.detach()
+    for py in range(2):
+        for px in range(2):
+            for ty in range(2):
+                for tx in range(2):
+                    ky, kx = _CONVT_TAPS[py][ty], _CONVT_TAPS[px][tx]
+                    if ky is not None and kx is not None:
+                        out[2 * py + px, :, ty, tx] = wd[:, :, ky, kx].transpose(0, 1)
+    return out.reshape(4, n, 4 * c).contiguous()
+
+
+def pack_convT3x3_s2_conv3x3(w: torch.Tensor) -> torch.Tensor:
+    """The same transposed conv for geometries tg_conv_up2 does not take: [C, N, 3, 3] -> [4*N, 9*C], the tap-major weight of a stride-1 pad-1 3x3 conv
+    (tg_gemm mode 1) on the LOW-resolution grid with 4 N output channels; channel (2 py + px) N + n of low-resolution pixel (i, j) is output pixel
+    (2i + py, 2j + px), channel n (layout 2 of tg_lineart_instnorm).  Conv tap (dy, dx) in {0, 1, 2} reads input pixel (i + dy - 1, j + dx - 1): row i is
+    dy = 1, row i + 1 is dy = 2 and dy = 0 stays zero; the conv's zero padding past the last row / column is ``output_padding=1``'s."""
+    c, n, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    out = torch.zeros(4, n, 3, 3, c, dtype=w.dtype, device=w.device)
+    wd = w.detach()
+    taps = (((1, 1),), ((1, 2), (2, 0)))           # [parity] -> (conv tap, transposed-conv tap) pairs
+    for py in range(2):
+        for px in range(2):
+            for dy, ky in taps[py]:
+                for dx, kx in taps[px]:
+                    out[2 * py + px, :, dy, dx] = wd[:, :, ky, kx].transpose(0, 1)
+    return out.reshape(4 * n, 9 * c).contiguous()
+
+
+def pack_conv7x7_fp32(w: torch.Tensor) -> torch.Tensor:
+    """Conv2d weight [N, C, 7, 7] -> fp32 [C * 49, N], row (c * 7 + ky) * 7 + kx (tg_lineart_conv7_in / _out read wave-uniform rows of output channels).
+    The VALUES stay the stored ones (an exact widening)."""
+    n, c, kh, kw = w.shape
+    assert kh == 7 and kw == 7
+    return w.detach().float().permute(1, 2, 3, 0).reshape(c * 49, n).contiguous()
+
+
+def pack_conv7x7_to1_fp32(w: torch.Tensor) -> torch.Tensor:
+    """Conv2d weight [1, C, 7, 7] -> fp32 [49, C], row ky * 7 + kx (tg_lineart_conv7_out: a thread's channels are contiguous)"""
+    n, c, kh, kw = w.shape
+    assert n == 1 and kh == 7 and kw == 7
+    return w.detach().float()[0].permute(1, 2, 0).reshape(49, c).contiguous()
 
 
 def pack_conv1x1(w: torch.Tensor) -> torch.Tensor:

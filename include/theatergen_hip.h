@@ -1147,6 +1147,49 @@ int tg_lineart_conv7_in(int32_t dtype, const void* x, int32_t batch, int32_t h, 
 int tg_lineart_conv7_out(int32_t dtype, const void* x, int32_t batch, int32_t h, int32_t w, const void* wt, float bias, void* out_u8,
                          void* out_sigmoid, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The annotator's two resizes (csrc/tg_cv_resize.hip): `cv2.resize(img, ..., INTER_AREA)` in front of the lineart network and
+ * `cv2.resize(map, ..., INTER_LINEAR)` behind it (controlnet_aux LineartDetector.__call__ with detect_resolution <= the short side).  Additive to ABI 308:
+ * two new symbols.  The arithmetic is OpenCV's portable C++ path (modules/imgproc/src/resize.cpp) as restated here; it was written from that source and
+ * has not been run against a cv2 build (an IPP or FMA-contracting build may differ).  tests/cv_resize_reference.py is the same statement in NumPy; the
+ * kernels are bit-equal to it.  The per-axis tables come from the host (theatergen_amd/cv_resize.py), made in float64 / integers.
+ *
+ * tg_cv_area_u8: src uint8 [batch, hs, ws, 3] -> dst NCHW [batch, 3, hd, wd] in dst_dtype (TG_BF16, TG_F16 or 2 = fp32) = byte / 255 (tg_image_from_u8,
+ *   range_mode 0, bit for bit) of the INTER_AREA result; u8_out (or NULL): those bytes, uint8 [batch, hd, wd, 3].  hd <= hs and wd <= ws.  One launch.
+ *   With scale = in / out in double per axis:
+ *     both scales integers (|scale - int(scale)| < DBL_EPSILON): the int32 sum of the sy x sx block; 2 x 2 gives (sum + 2) >> 2, anything else (1 x 1,
+ *       the copy, included) round-half-even(float(sum) * float32(1 / (sx sy))).  The tables are not read (may be NULL).
+ *     otherwise, per axis, destination index d has `count[d]` entries on consecutive source indices from `first[d]` with weights alpha[d][0 .. count):
+ *       f1 = d scale, f2 = f1 + scale, cell = min(scale, in - f1), s1 = ceil(f1), s2 = min(floor(f2), in - 1), s1 = min(s1, s2);
+ *       if s1 - f1 > 1e-3: (s1 - 1, float32((s1 - f1) / cell)); for s in [s1, s2): (s, float32(1 / cell));
+ *       if f2 - s2 > 1e-3: (s2, float32(min(min(f2 - s2, 1), cell) / cell)).
+ *       For each vertical entry (sy, beta) of a destination row, in order: buf[dx] = sum over the horizontal entries, from 0 and in order, of
+ *       float(S[sy][sx]) * alpha, then sum = beta * buf (first entry) or sum + beta * buf; every product and every sum is one fp32 operation, never
+ *       fused.  The byte is round-half-even(sum) saturated to 0 .. 255.
+ *   ksize_v / ksize_h: the row length of alpha_v / alpha_h, 1 .. TG_CV_AREA_MAX_TAPS.  stage_rows: the largest number of source rows the vertical entries
+ *   of 4 consecutive destination rows (rows 4 i .. 4 i + 3) span, first[last] + count[last] - first[4 i]; 1 .. TG_CV_AREA_STAGE_ROWS.
+ *   TG_ERR_ARG before any launch: a null src / dst; aliased buffers; batch or a size outside 1 .. TG_CV_RESIZE_MAX_SIZE; a growing axis; a bad dtype;
+ *   on the general route a null table, a ksize or a stage_rows outside its range.
+ *
+ * tg_cv_linear_u8: src uint8 [batch, hs, ws, 3] whose three channels are equal (tg_lineart_conv7_out's map; channel 0 is read) -> the INTER_LINEAR
+ *   result at [hd, wd], any direction, no antialiasing: u8_out (or NULL) uint8 [batch, hd, wd, 3], the value three times, and / or dst (or NULL) NCHW
+ *   [batch, 3, hd, wd] = byte / 255 in dst_dtype, the control image.  tab_v [hd][4] / tab_h [wd][4] int32, 16-byte aligned, entry (s0, s1, c0, c1):
+ *     f = float32((d + 0.5) scale - 0.5), s = floor(f), f -= s; s < 0: s = 0, f = 0; s >= in - 1: s = in - 1, f = 0; s0 = s, s1 = min(s + 1, in - 1),
+ *     c0 = sat_int16(rint(float32(1 - f) * 2048)), c1 = sat_int16(rint(f * 2048)).
+ *   In int32 with arithmetic shifts: r = S[s0] a0 + S[s1] a1 per source row, out = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2,
+ *   saturated to 0 .. 255.  invert = 1: S is 255 - src and the stored byte is 255 - out: resize first, then invert, the annotator's order, on a source
+ *   that already holds the inverted map (the fixed-point rounding does not commute with the inversion).
+ *   TG_ERR_ARG before any launch: a null src / table; neither output; aliased buffers; batch or a size outside 1 .. TG_CV_RESIZE_MAX_SIZE; invert not
+ *   0 / 1; a bad dtype with dst; a misaligned table. */
+#define TG_CV_AREA_MAX_TAPS 8
+#define TG_CV_AREA_STAGE_ROWS 32
+#define TG_CV_RESIZE_MAX_SIZE 8192
+int tg_cv_area_u8(const void* src, int32_t batch, int32_t hs, int32_t ws, int32_t hd, int32_t wd, const int32_t* first_v, const int32_t* count_v,
+                  const float* alpha_v, int32_t ksize_v, const int32_t* first_h, const int32_t* count_h, const float* alpha_h, int32_t ksize_h,
+                  int32_t stage_rows, void* dst, int32_t dst_dtype, void* u8_out, void* stream);
+int tg_cv_linear_u8(const void* src, int32_t batch, int32_t hs, int32_t ws, int32_t hd, int32_t wd, const int32_t* tab_v, const int32_t* tab_h,
+                    int32_t invert, void* u8_out, void* dst, int32_t dst_dtype, void* stream);
+
 /* debugging aid: raw 32x32x16 MFMA on caller-provided fragments (64 lanes x 8 elements each) */
 int tg_debug_mfma32(int32_t dtype, const void* a_frags, const void* b_frags, float* d_out, void* stream);
 

@@ -17,6 +17,8 @@ ACT_NONE, ACT_SILU, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2, 3
 RC_FF_TWO_WAVE = 0x10000     # TG_RC_FF_TWO_WAVE: the stream-format tag (pack_ff2 / pack_po2) the `dbg` word of tg_rc_ff_desc must hold
 # TG_RESAMPLE_TILE_H / _TILE_W / _LDS_BYTES / _MAX_SIZE: the fused tile of tg_image_resample_u8 and its LDS budget (the host plan picks the route with them)
 RESAMPLE_TILE_H, RESAMPLE_TILE_W, RESAMPLE_LDS_BYTES, RESAMPLE_MAX_SIZE = 16, 128, 20480, 8192
+# TG_CV_AREA_MAX_TAPS / _STAGE_ROWS, TG_CV_RESIZE_MAX_SIZE: what tg_cv_area_u8's general route holds per axis and per 4-row tile (cv_resize.py plans with them)
+CV_AREA_MAX_TAPS, CV_AREA_STAGE_ROWS, CV_AREA_TILE_H, CV_RESIZE_MAX_SIZE = 8, 32, 4, 8192
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -226,6 +228,8 @@ SIGNATURES = {
     "tg_lineart_instnorm": (i32, [i32, vp, i32, i32, i32, i32, i32, f32, i32, vp, i32, vp, i32, vp, vp]),
     "tg_lineart_conv7_in": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp]),
     "tg_lineart_conv7_out": (i32, [i32, vp, i32, i32, i32, vp, f32, vp, vp, vp]),
+    "tg_cv_area_u8": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp]),
+    "tg_cv_linear_u8": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp]),
     "tg_debug_mfma32": (i32, [i32, vp, vp, vp, vp]),
 }
 

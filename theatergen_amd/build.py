@@ -209,6 +209,12 @@ HOT_GATES = [
     ("lineart_in_stats_kernel<", 0, 46),
     ("lineart_in_finalize_kernel", 0, 21),
     ("lineart_in_apply_kernel<", 0, 38),
+    # the annotator's INTER_AREA / INTER_LINEAR resizes (tg_cv_resize.hip; <T>).  The general AREA kernel keeps three fp32 sums per pass and stages 24 KiB
+    # (six workgroups per CU); the block-sum kernel three int32 sums; the LINEAR kernel four pixels per thread (two 16-byte LDS reads, the packed 12-byte
+    # store) — scratch would mean one of those small arrays was indexed at run time.  Allowances = what the build reports
+    ("cv_area_kernel<", 0, 52),
+    ("cv_area_int_kernel<", 0, 24),
+    ("cv_linear_kernel<", 0, 50),
 ]
 
 

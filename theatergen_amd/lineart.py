@@ -19,9 +19,15 @@ Device route (no torch arithmetic; activations token-major NHWC in the storage d
     (512 x 512: widths 128 and 256) it is one pad-1 ``ops.conv3x3`` on the low-resolution grid with 4 N output channels, one block of N per output parity
     class (``pack_convT3x3_s2_conv3x3``: the unused taps are zero weights), and the following InstanceNorm reads that layout: no pixel-shuffle pass.
 
-``LineartDetector`` is the annotator's ``__call__`` for the case both of its cv2 resizes are the identity (the SD-1.5 / SD-2.1 flow: a 512 x 512 image at
-``detect_resolution = image_resolution = 512``); anything that would need cv2's LANCZOS4 / AREA filters raises NotImplementedError.
+``LineartDetector`` is the annotator's ``__call__`` for every call whose detect step shrinks the image or leaves its size alone (``detect_resolution`` <=
+the short side): ``cv2.resize(..., INTER_AREA)`` in front of the network and ``cv2.resize(..., INTER_LINEAR)`` + ``255 - map`` behind it are the kernels
+of csrc/tg_cv_resize.hip, in the arithmetic of OpenCV's portable C++ path as include/theatergen_hip.h restates it (written from resize.cpp, not run
+against a cv2 build).  The SD-1.5 / SD-2.1 flow (a 512 x 512 image at 512 / 512) needs neither and runs as before; the SDXL flow (1024 x 1024 at
+``detect_resolution=384, image_resolution=1024``) needs both.  A ``detect_resolution`` above the short side would need LANCZOS4 pixels and raises
+NotImplementedError.
 """
+import collections
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -146,13 +152,43 @@ def resized_size(h, w, resolution):
 
 
 def check_identity_resize(h, w, detect_resolution, image_resolution):
-    """The detector is built for the case both of the annotator's cv2 resizes are the identity; anything else raises NotImplementedError"""
+    """The predicate of the route with no resize launch: both of the annotator's cv2 resizes are the identity; anything else raises NotImplementedError
+    (``plan_resizes`` is what the detector asks; this stays for callers that need exactly the identity case)"""
     for what, res in (("detect_resolution", detect_resolution), ("image_resolution", image_resolution)):
         got = resized_size(h, w, res)
         if got != (h, w):
             raise NotImplementedError(
                 f"LineartDetector: {what}={res} would resize the {h} x {w} image to {got[0]} x {got[1]} with cv2's LANCZOS4 / AREA filters, which are "
                 "not built here (only the identity case: sides that are multiples of 64 with the short side equal to both resolutions)")
+
+
+LineartPlan = collections.namedtuple("LineartPlan", "net out area linear")
+
+
+def plan_resizes(h, w, detect_resolution, image_resolution):
+    """The annotator's two resizes for an h x w image -> ``LineartPlan(net, out, area, linear)``: ``net`` = (H, W) of ``resize_image(image,
+    detect_resolution)``, what the network runs at; ``out`` = (H, W) of ``resize_image(<that image>, image_resolution)``, what the map is resized to (the
+    annotator computes that second image only for its shape); ``area`` / ``linear``: whether the INTER_AREA launch in front of the network and the
+    INTER_LINEAR launch behind it are needed (a size that does not change needs none: the identity case keeps its launches and its bytes).
+    ``resize_image`` takes INTER_AREA when its factor k = resolution / short side is <= 1 and LANCZOS4 otherwise; LANCZOS4 pixels are needed only at the
+    detect step (k > 1 there: NotImplementedError), and so is an INTER_AREA call that grows an axis (k < 1 with a side rounded up to a multiple of 64)."""
+    h, w = int(h), int(w)
+    if float(detect_resolution) / min(h, w) > 1:
+        got = resized_size(h, w, detect_resolution)
+        raise NotImplementedError(
+            f"LineartDetector: detect_resolution={detect_resolution} is above the short side of the {h} x {w} image: the annotator would enlarge it to "
+            f"{got[0]} x {got[1]} with cv2's LANCZOS4 filter, which is not built here (INTER_AREA in front of the network and INTER_LINEAR behind it are)")
+    net = resized_size(h, w, detect_resolution)
+    if net[0] < 64 or net[1] < 64:
+        raise ValueError(f"LineartDetector: detect_resolution={detect_resolution} gives a {net[0]} x {net[1]} network input for the {h} x {w} image")
+    if net[0] > h or net[1] > w:
+        raise NotImplementedError(
+            f"LineartDetector: detect_resolution={detect_resolution} rounds the {h} x {w} image to {net[0]} x {net[1]}: cv2's INTER_AREA on a growing axis "
+            "(where it interpolates linearly) is not built here")
+    out = resized_size(net[0], net[1], image_resolution)
+    if out[0] < 1 or out[1] < 1:
+        raise ValueError(f"LineartDetector: image_resolution={image_resolution} gives a {out[0]} x {out[1]} control image")
+    return LineartPlan(net, out, net != (h, w), out != net)
 
 
 def _to_u8_hwc3(image, device):
@@ -220,8 +256,10 @@ class LineartDetector:
             self.model_coarse.to(*args, **kw)
         return self
 
-    def _maps(self, images, coarse, detect_resolution, image_resolution):
-        """list of images of one size -> device uint8 [B, H, W, 3]: the control images"""
+    def _maps(self, images, coarse, detect_resolution, image_resolution, want_pt=False):
+        """list of images of one size -> (device uint8 [B, H, W, 3] or None, device [B, 3, H, W] in the model dtype or None): the control images.  The
+        float form comes back only from the INTER_LINEAR launch with ``want_pt`` (then the bytes are not written at all); every other route returns the
+        bytes and ``_output`` converts them."""
         model = self.model_coarse if coarse else self.model
         if model is None:
             raise ValueError("LineartDetector: coarse=True needs a coarse model (model_coarse is None)")
@@ -229,32 +267,46 @@ class LineartDetector:
         H, W = u8[0].shape[:2]
         if any(tuple(t.shape) != (H, W, 3) for t in u8):
             raise ValueError("LineartDetector.detect_many: all images must have one size")
-        check_identity_resize(H, W, detect_resolution, image_resolution)
-        x = ops.image_from_u8(torch.stack(u8) if len(u8) > 1 else u8[0][None], model.dtype, range_mode=0)
-        return model(x)
+        plan = plan_resizes(H, W, detect_resolution, image_resolution)              # raises before any device work
+        batch = torch.stack(u8) if len(u8) > 1 else u8[0][None]
+        if plan.area:
+            x = ops.cv_area_u8(batch, plan.net, model.dtype)
+        else:
+            x = ops.image_from_u8(batch, model.dtype, range_mode=0)
+        maps = model(x)                                                             # 255 - t, three times
+        if not plan.linear:
+            return maps, None
+        if want_pt:
+            return None, ops.cv_linear_u8(maps, plan.out, invert=True, dtype=model.dtype, u8_out=False)
+        return ops.cv_linear_u8(maps, plan.out, invert=True), None
 
-    def _output(self, u8, output_type):
-        """u8: device uint8 [H, W, 3]"""
-        output_type = output_type or self.output_type
+    def _output(self, u8, pt, i, output_type):
+        """image i of u8 (device uint8 [B, H, W, 3]) or of pt (device [B, 3, H, W])"""
         if output_type == "pt":
-            return ops.image_from_u8(u8[None], self.model.dtype, range_mode=0)
-        arr = u8.cpu().numpy()
+            return pt[i:i + 1] if pt is not None else ops.image_from_u8(u8[i][None], self.model.dtype, range_mode=0)
+        arr = u8[i].cpu().numpy()
         if output_type == "np":
             return arr
-        if output_type != "pil":
-            raise ValueError(f"LineartDetector: output_type must be 'pil', 'pt' or 'np', got {output_type!r}")
         from PIL import Image
         return Image.fromarray(arr)
 
+    def _output_type(self, output_type):
+        output_type = output_type or self.output_type
+        if output_type not in ("pil", "pt", "np"):
+            raise ValueError(f"LineartDetector: output_type must be 'pil', 'pt' or 'np', got {output_type!r}")
+        return output_type
+
     @torch.no_grad()
     def __call__(self, input_image, coarse=False, detect_resolution=512, image_resolution=512, output_type=None):
-        return self._output(self._maps([input_image], coarse, detect_resolution, image_resolution)[0], output_type)
+        return self.detect_many([input_image], coarse, detect_resolution, image_resolution, output_type)[0]
 
     @torch.no_grad()
     def detect_many(self, images, coarse=False, detect_resolution=512, image_resolution=512, output_type=None):
-        """A list of images of one size in ONE batched forward (InstanceNorm is per image: the same bytes as the single calls) -> list of outputs"""
+        """A list of images of one size in ONE batched forward (InstanceNorm is per image, the resizes too: the same bytes as the single calls) -> list
+        of outputs"""
         images = list(images)
         if not images:
             return []
-        maps = self._maps(images, coarse, detect_resolution, image_resolution)
-        return [self._output(maps[i], output_type) for i in range(len(images))]
+        output_type = self._output_type(output_type)
+        u8, pt = self._maps(images, coarse, detect_resolution, image_resolution, want_pt=output_type == "pt")
+        return [self._output(u8, pt, i, output_type) for i in range(len(images))]

@@ -1485,6 +1485,82 @@ def image_resample_u8(images, plan_v, plan_h, lut, dtype, window=None, pad=None,
     return out if u8_out is None else (out, u8_out)
 
 
+def cv_area_u8(images, size, dtype, out=None, u8_out=None):
+    """``cv2.resize(image, (wd, hd), interpolation=cv2.INTER_AREA)`` of uint8 RGB ``[B, hs, ws, 3]`` on the device (``size`` = (hd, wd), neither axis
+    growing), then ``byte / 255`` as NCHW ``[B, 3, hd, wd]`` in ``dtype`` (bf16 / fp16 / fp32): bit-equal to ``image_from_u8(resized, dtype,
+    range_mode=0)``, in one launch.  ``u8_out``: a uint8 ``[B, hd, wd, 3]`` tensor, or True to allocate one: the resized bytes, returned as the second
+    value.  The arithmetic is OpenCV's portable C++ path as tg_cv_area_u8 in include/theatergen_hip.h restates it (not run against a cv2 build)."""
+    from . import cv_resize
+    _need_cuda(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+        raise ValueError(f"cv_area_u8: uint8 [B, H, W, 3] expected, got {images.dtype} {tuple(images.shape)}")
+    if dtype not in _SRC:
+        raise RuntimeError(f"theatergen_amd: cv_area_u8 writes bf16 / fp16 / fp32, not {dtype}")
+    B, hs, ws, _ = (int(v) for v in images.shape)
+    hd, wd = int(size[0]), int(size[1])
+    if hd > hs or wd > ws or hd < 1 or wd < 1:
+        raise NotImplementedError(f"cv_area_u8: {(hs, ws)} -> {(hd, wd)}: INTER_AREA is built for shrinking or equal axes only")
+    images = images.contiguous()
+    if out is None:
+        out = torch.empty((B, 3, hd, wd), dtype=dtype, device=images.device)
+    elif tuple(out.shape) != (B, 3, hd, wd) or out.dtype != dtype or not out.is_contiguous() or out.device != images.device:
+        raise ValueError(f"cv_area_u8: out must be a contiguous {dtype} tensor of shape {(B, 3, hd, wd)} on the images' device")
+    if u8_out is True:
+        u8_out = torch.empty((B, hd, wd, 3), dtype=torch.uint8, device=images.device)
+    elif u8_out is not None and (tuple(u8_out.shape) != (B, hd, wd, 3) or u8_out.dtype != torch.uint8 or not u8_out.is_contiguous()
+                                 or u8_out.device != images.device):
+        raise ValueError(f"cv_area_u8: u8_out must be a contiguous uint8 tensor of shape {(B, hd, wd, 3)} on the images' device")
+    if cv_resize.area_is_integer(hs, hd) and cv_resize.area_is_integer(ws, wd):
+        tables, rows = (None, None, None, 0, None, None, None, 0), 0
+    else:
+        (pv, fv, cv, av), (ph, fh, ch, ah) = cv_resize.device_area_plan(hs, hd, images.device), cv_resize.device_area_plan(ws, wd, images.device)
+        rows = cv_resize.area_stage_rows(pv)
+        if rows > _lib.CV_AREA_STAGE_ROWS:
+            raise NotImplementedError(f"cv_area_u8: {hs} -> {hd} rows: a tile's vertical entries span {rows} source rows; the kernel stages "
+                                      f"{_lib.CV_AREA_STAGE_ROWS}")
+        tables = (_ptr(fv), _ptr(cv), _ptr(av), int(av.shape[1]), _ptr(fh), _ptr(ch), _ptr(ah), int(ah.shape[1]))
+    _lib.check(_lib.lib().tg_cv_area_u8(_ptr(images), B, hs, ws, hd, wd, *tables, rows, _ptr(out), _SRC[dtype], _ptr(u8_out), _stream()))
+    return out if u8_out is None else (out, u8_out)
+
+
+def cv_linear_u8(images, size, invert=False, dtype=None, u8_out=True, out=None):
+    """``cv2.resize(map, (wd, hd), interpolation=cv2.INTER_LINEAR)`` (no antialiasing, either direction) of a uint8 ``[B, hs, ws, 3]`` map whose three
+    channels are equal (``lineart_conv7_out``'s; channel 0 is read), ``size`` = (hd, wd).  ``invert``: the map holds ``255 - t``; the kernel resizes ``t``
+    and stores ``255 - result`` (the annotator's order: the fixed-point rounding does not commute with the inversion).  Outputs: ``u8_out`` (True to
+    allocate, a tensor, or None / False) uint8 ``[B, hd, wd, 3]``; with ``dtype`` (or ``out``) also ``byte / 255`` as NCHW ``[B, 3, hd, wd]`` in bf16 /
+    fp16 / fp32, the control image.  Returns the uint8 tensor, the float tensor, or ``(uint8, float)`` when both are asked for.  See tg_cv_linear_u8."""
+    from . import cv_resize
+    _need_cuda(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+        raise ValueError(f"cv_linear_u8: uint8 [B, H, W, 3] expected, got {images.dtype} {tuple(images.shape)}")
+    B, hs, ws, _ = (int(v) for v in images.shape)
+    hd, wd = int(size[0]), int(size[1])
+    if out is not None:
+        dtype = out.dtype
+    if dtype is not None and dtype not in _SRC:
+        raise RuntimeError(f"theatergen_amd: cv_linear_u8 writes bf16 / fp16 / fp32, not {dtype}")
+    images = images.contiguous()
+    if u8_out is True:
+        u8_out = torch.empty((B, hd, wd, 3), dtype=torch.uint8, device=images.device)
+    elif u8_out is False:
+        u8_out = None
+    elif u8_out is not None and (tuple(u8_out.shape) != (B, hd, wd, 3) or u8_out.dtype != torch.uint8 or not u8_out.is_contiguous()
+                                 or u8_out.device != images.device):
+        raise ValueError(f"cv_linear_u8: u8_out must be a contiguous uint8 tensor of shape {(B, hd, wd, 3)} on the images' device")
+    if dtype is not None and out is None:
+        out = torch.empty((B, 3, hd, wd), dtype=dtype, device=images.device)
+    elif out is not None and (tuple(out.shape) != (B, 3, hd, wd) or not out.is_contiguous() or out.device != images.device):
+        raise ValueError(f"cv_linear_u8: out must be a contiguous tensor of shape {(B, 3, hd, wd)} on the images' device")
+    if u8_out is None and out is None:
+        raise ValueError("cv_linear_u8: no output asked for (u8_out, dtype / out, or both)")
+    (_, tv), (_, th) = cv_resize.device_linear_plan(hs, hd, images.device), cv_resize.device_linear_plan(ws, wd, images.device)
+    _lib.check(_lib.lib().tg_cv_linear_u8(_ptr(images), B, hs, ws, hd, wd, _ptr(tv), _ptr(th), 1 if invert else 0, _ptr(u8_out), _ptr(out),
+                                          _SRC[dtype] if dtype is not None else 0, _stream()))
+    if u8_out is None:
+        return out
+    return u8_out if out is None else (u8_out, out)
+
+
 def blend_latents(bg, fg, mask, ratio, sigma=1.0, storage_dtype=None):
     """fp32 in / out; ``storage_dtype`` torch.float16 / torch.bfloat16: reproduce the half-precision roundings of the
     reference expression (its latents are ``unet.dtype`` tensors)"""
